@@ -1,7 +1,7 @@
 """Benchmark of the MI355X MU hot path (BASELINE.json metric: MU iterations/sec & achieved HBM
 GB/s vs peak, V = 1e6 x 81, k = 4, at 1/2/4/8 GPUs; configs[1] = cfg2 at one GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     torchrun --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
     python bench.py --rows 10000000 --k 8             # cfg3's rows on one GPU
     python bench.py --rows 10000000 --k 8 --scaling strong   # cfg3 as one 1e7-row problem over the GPUs
@@ -21,7 +21,7 @@ the it/s of the problem run).  --scaling strong: V = --rows x 81 is ONE problem 
 cfg3's) split over the N ranks in 64-row-aligned shards, value = iterations/s of that problem
 (unit "it/s").
 
-At N > 1 the line also carries `strong`: the metric's own V = --strong-rows (default 1e6) x 81
+At N > 1 with --full the line also carries `strong`: the metric's own V = --strong-rows (default 1e6) x 81
 problem — cfg2's X and start, split over the same ranks — timed in the same run, and the same
 problem on rank 0's GPU alone, so `strong.speedup_vs_n1` is north_star's strong-scaling figure
 measured on one clock.  At N = 1 `strong` is the line itself.
@@ -32,8 +32,15 @@ entry of W or H on any rank, exits with status 3 and prints no line.
 Extra keys: roofline (the dominant kernel timed with HIP events on its launch stream inside the
 timed region: at N = 1 the ONE persistent launch that runs all K iterations, else each per-iteration
 launch; achieved = algorithmic bytes of this GPU's shard n·(F·4 + 2·k·4) per iteration × iterations
-per launch ÷ the slowest rank's launch time, peak = one MI355X's 8 TB/s), cpu_baseline (the NumPy /
-scipy oracle, rank 0 at N = 1 only, bounded sample).
+per launch ÷ the slowest rank's launch time, peak = one MI355X's 8 TB/s).
+
+A plain run does only what the line's headline figure needs: set up, warm up (with the clock ramp and
+the layout tuning), time the K steps, print the line.  --full adds the measurements that are runs of
+their own: cpu_baseline (the NumPy / scipy oracle, rank 0 at N = 1 only, bounded sample; --no-cpu
+leaves it out) and, at N > 1, the `strong` split with its one-GPU reference; without --full those
+keys are null.  --dump-outputs DIR writes W and H as they stand after the last timed step (DIR/W.npy,
+DIR/H.npy); the inputs are seeded, so two builds run with the same arguments can be compared output
+for output.
 """
 from __future__ import annotations
 
@@ -51,6 +58,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip-level parameters)
 EXIT_BROKEN = 3  # a run whose final state is not a valid factorisation: no line is printed
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much
 
 
 def parse(argv=None):
@@ -69,7 +77,7 @@ def parse(argv=None):
                         "'<rows>-row it/s'; strong: --rows is ONE problem split over the GPUs, value = "
                         "iterations/s of that problem")
     p.add_argument("--strong-rows", type=int, default=None,
-                   help="at N > 1: also time this V (x F) as ONE problem split over the ranks, and on "
+                   help="at N > 1 with --full: also time this V (x F) as ONE problem split over the ranks, and on "
                         "rank 0's GPU alone (the line's `strong` key); 0 = skip; default 1e6 (the "
                         "metric's V), skipped when ranks share a GPU (their 1e6-row persistent grids "
                         "are not co-resident on one device; ADVICE r5)")
@@ -114,7 +122,40 @@ def parse(argv=None):
                         "gloo (host-side collectives: lets two ranks share one GPU, as the N > 1 tests do)")
     p.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"),
                    help="PMC traffic summary written by tools/pmc_traffic.py (optional)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beside the headline figure: the CPU baseline (unless "
+                        "--no-cpu) and, at N > 1, the `strong` split with its one-GPU reference; without "
+                        "it those keys of the line are null")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write the factors the timed path holds after its last "
+                        f"step as DIR/W.npy (float32; float64 at --dtype f64) and DIR/H.npy (float64), at most {DUMP_MAX_BYTES // 10**6} "
+                        "MB in all (a seeded row sample of a larger W, its rows in DIR/W_rows.npy)")
     return p.parse_args(argv)
+
+
+def dump_outputs(path: str, W, H, seed: int = 0, max_bytes: int | None = None) -> dict:
+    """Write what a caller of the timed path receives after its last step: W (n x k, this rank's
+    rows; float32, float64 at --dtype f64) and H (k x F, float64) as <path>/W.npy and <path>/H.npy.
+    A W that would take the
+    files past max_bytes is cut to a fixed sample of its rows (sorted, drawn with `seed`), whose
+    indices go to <path>/W_rows.npy.  Returns {file name: shape}."""
+    max_bytes = DUMP_MAX_BYTES if max_bytes is None else max_bytes
+    os.makedirs(path, exist_ok=True)
+    W = np.asarray(W)
+    W = np.ascontiguousarray(W, dtype=np.float64 if W.dtype == np.float64 else np.float32)
+    H = np.ascontiguousarray(np.asarray(H, dtype=np.float64))
+    out = {}
+    room = max_bytes - H.nbytes - 3 * 128  # the three .npy headers
+    if W.nbytes > room:
+        n_keep = max(int(room // (W.shape[1] * W.itemsize + 8)), 1)  # a row + its index (as float64: exact)
+        rows = np.sort(np.random.default_rng(seed).choice(W.shape[0], size=n_keep, replace=False))
+        W = np.ascontiguousarray(W[rows])
+        np.save(os.path.join(path, "W_rows.npy"), rows.astype(np.float64))
+        out["W_rows.npy"] = list(rows.shape)
+    np.save(os.path.join(path, "W.npy"), W)
+    np.save(os.path.join(path, "H.npy"), H)
+    out["W.npy"], out["H.npy"] = list(W.shape), list(H.shape)
+    return out
 
 
 def cpu_model() -> str:
@@ -683,7 +724,9 @@ def main():
         if world > 1 and n_gpus < world:
             S, strong_skipped = 0, (f"not measured: {world} ranks share {n_gpus} GPU(s) (pass --strong-rows "
                                     f"to split a problem whose per-rank grids are co-resident)")
-    if world > 1 and S > 0:
+    if world > 1 and not args.full:  # the split and its one-GPU reference are runs of their own
+        pass
+    elif world > 1 and S > 0:
         if args.scaling == "strong" and S == args.rows:
             sres, s_rows, s_plan = res, n_rows, None
         else:
@@ -722,6 +765,11 @@ def main():
             dist.barrier()
             dist.destroy_process_group()
         return
+
+    if args.dump_outputs:  # rank 0's rows of W (at N = 1 all of them) and H, the same on every rank
+        dumped = dump_outputs(args.dump_outputs, plan.W.detach().cpu().numpy(), plan.H64.detach().cpu().numpy())
+        print(f"[bench] outputs after the last timed step written to {args.dump_outputs}: {dumped}",
+              file=sys.stderr, flush=True)
 
     persistent = res["persistent"]
     tol_result = res["tol_result"]
@@ -771,7 +819,7 @@ def main():
                 "max_over_ranks_avg_launch_us": round(avg_pass_s_max * 1e6, 2)}
 
     cpu = None
-    if world == 1 and not args.no_cpu and not args.weighted:
+    if args.full and world == 1 and not args.no_cpu and not args.weighted:
         Xc = X if args.dtype != "bf16" else Xt.float().numpy()
         if args.solver == "als":
             cpu = cpu_baseline_als(Xc, W0, H0, args.sum_to_one, args.smoothness, args.cpu_seconds)

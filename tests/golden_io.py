@@ -33,6 +33,16 @@ def load_init(name):
     return case
 
 
+def load_tall(name):
+    """A tall default-init case (make_golden.py:tall_cases) as one dict of arrays: sklearn's result
+    (<name>.npz) and its start W_init / H_init (<name>_start.npz; two files, each under 1 MiB)."""
+    case = {}
+    for part in (f"{name}.npz", f"{name}_start.npz"):
+        z = np.load(os.path.join(GOLDEN, part), allow_pickle=False)
+        case.update({k: z[k] for k in z.files})
+    return case
+
+
 def rel_fro(a, b):
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)

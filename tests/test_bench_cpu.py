@@ -213,3 +213,37 @@ def test_gpus_flag_without_launcher_never_reports_one_rank():
         assert r.returncode != 0
     r = _bench_cmd(["--gpus", "2"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode == 2 and "refused" in r.stderr and '"n_gpus"' not in r.stdout
+
+
+def test_full_and_dump_outputs_flags_parse(monkeypatch):
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """W and H go out whole under the size cap; a larger W as the same seeded row sample every time,
+    with its row indices, and the files stay under the cap."""
+    import numpy as np
+    rng = np.random.default_rng(0)
+    W = rng.random((1000, 4)).astype(np.float32)
+    H = rng.random((4, 81))
+    shapes = bench.dump_outputs(str(tmp_path / "a"), W, H)
+    assert shapes == {"W.npy": [1000, 4], "H.npy": [4, 81]}
+    Wd, Hd = np.load(tmp_path / "a" / "W.npy"), np.load(tmp_path / "a" / "H.npy")
+    assert Wd.dtype == np.float32 and Hd.dtype == np.float64
+    assert np.array_equal(Wd, W) and np.array_equal(Hd, H)
+
+    cap = 8000
+    for name in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / name), W, H, max_bytes=cap)
+    rows = np.load(tmp_path / "b" / "W_rows.npy")
+    assert rows.dtype == np.float64 and 0 < len(rows) < 1000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "W.npy"), W[rows.astype(np.int64)])
+    for f in ("W.npy", "W_rows.npy", "H.npy"):
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= cap
+    assert bench.DUMP_MAX_BYTES <= 64 * 1000 * 1000

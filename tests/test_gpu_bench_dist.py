@@ -28,8 +28,8 @@ def _free_port():
 
 def _run_two_ranks(extra, timeout=240, rank_env=None):
     """bench.py's two ranks on cuda:0; rank_env: {rank: {VAR: value}} added to that rank's environment
-    (the fault-injection switches of cnmf_amd/solver.py).  Without --strong-rows the bench records the
-    default 1e6-row split as not measured (ranks sharing a GPU)."""
+    (the fault-injection switches of cnmf_amd/solver.py).  With --full and without --strong-rows the
+    bench records the default 1e6-row split as not measured (ranks sharing a GPU)."""
     port = _free_port()
     procs = []
     for rank in range(2):
@@ -59,7 +59,7 @@ def _run_two_ranks(extra, timeout=240, rank_env=None):
 
 @pytest.mark.timeout(300)
 def test_bench_two_ranks_one_gpu_exchange():
-    res, outs = _run_two_ranks(["--rows", "32768"])
+    res, outs = _run_two_ranks(["--rows", "32768", "--full"])
     cfg = res["config"]
     assert res["ranks"] == 2 and res["n_gpus"] == 1 and res["value"] > 0  # two ranks sharing one GPU
     assert cfg["exchange"].startswith("validated"), cfg["exchange"]
@@ -105,7 +105,8 @@ def test_bench_exchange_poisoned_launch_moves_every_rank_to_rccl():
 def test_bench_two_ranks_weighted_with_strong_split():
     """--weighted at N = 2 through the whole bench, the strong split included (its plan is
     released after the measurement): one line, the exchange validated for the weighted launch."""
-    res, outs = _run_two_ranks(["--rows", "16384", "--scaling", "weak", "--weighted", "--strong-rows", "32768"])
+    res, outs = _run_two_ranks(["--rows", "16384", "--scaling", "weak", "--weighted", "--strong-rows", "32768",
+                                "--full"])
     assert res["ranks"] == 2 and res["value"] > 0
     assert res["config"]["exchange"].startswith("validated"), res["config"]["exchange"]
     assert res["strong"]["rows"] == 32768 and res["strong"]["speedup_vs_n1"] > 0
@@ -141,7 +142,7 @@ def test_bench_two_ranks_strong_split_beside_the_weak_line():
     """at N > 1 the line carries the fixed problem (here 32768 rows, the metric's
     V = 1e6 on the driver's nodes) split over the same ranks and timed in the same run, and the same
     problem on rank 0's GPU alone: it/s, us per iteration, HBM fraction, speed-up over one GPU."""
-    res, outs = _run_two_ranks(["--rows", "16384", "--scaling", "weak", "--strong-rows", "32768"])
+    res, outs = _run_two_ranks(["--rows", "16384", "--scaling", "weak", "--strong-rows", "32768", "--full"])
     assert res["unit"] == "16384-row it/s" and res["scaling"] == "weak"
     st = res["strong"]
     assert st["rows"] == 32768 and st["ranks"] == 2 and st["rows_per_gpu_max"] == 16384
@@ -165,3 +166,50 @@ def test_bench_one_gpu_line_carries_strong_as_itself():
     assert res["unit"] == "65536-row it/s" and res["n_gpus"] == 1
     assert res["strong"]["speedup_vs_n1"] == 1.0 and res["strong"]["rows"] == 65536
     assert abs(res["strong"]["it_s"] - res["value"]) <= 0.01 * res["value"]
+
+
+def _run_one_gpu(extra):
+    r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6",
+                        "--warmup", "4", "--ramp-seconds", "0.05", "--rows", "4099"] + extra,
+                       cwd=ROOT, capture_output=True, text=True, timeout=240,
+                       env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run leaves out the CPU baseline (null) and --full brings it back; --dump-outputs writes
+    W (float32) and H (float64) as they stand after the last timed step: the warmup + steps MU
+    iterations of the fp64 oracle from the same seeded start, at the parity bar (1e-5), and the same
+    from run to run."""
+    import numpy as np
+
+    from cnmf_amd.synthetic import iop_spectra, random_init
+    from oracle import mu_ref
+
+    plain = _run_one_gpu(["--dump-outputs", str(tmp_path / "plain")])
+    assert plain["cpu_baseline"] is None and plain["steps"] == 6 and plain["warmup"] == 4
+    assert plain["ms_per_step"] > 0 and plain["value"] > 0 and plain["unit"] == "4099-row it/s"
+    # one step = one iteration: value x ms_per_step = 1000, to the rounding of the two printed figures
+    # (ms_per_step to 4 decimals, value to 2)
+    assert abs(plain["value"] * plain["ms_per_step"] / 1e3 - 1.0) <= 1e-4 / plain["ms_per_step"] + 1e-3
+    assert sorted(os.listdir(tmp_path / "plain")) == ["H.npy", "W.npy"]
+    W, H = np.load(tmp_path / "plain" / "W.npy"), np.load(tmp_path / "plain" / "H.npy")
+    assert W.dtype == np.float32 and W.shape == (4099, 4) and H.dtype == np.float64 and H.shape == (4, 81)
+
+    X = iop_spectra(4099, 81, seed=0, dtype=np.float32)
+    W0, H0 = random_init(X, 4, 42)
+    Wr, Hr, _ = mu_ref.mu_fit(X.astype(np.float64), W0.astype(np.float64), H0.astype(np.float64),
+                              max_iter=10, tol=0.0)
+    assert np.linalg.norm(W - Wr) / np.linalg.norm(Wr) < 1e-5
+    assert np.linalg.norm(H - Hr) / np.linalg.norm(Hr) < 1e-5
+
+    full = _run_one_gpu(["--full", "--cpu-seconds", "0.3", "--dump-outputs", str(tmp_path / "full")])
+    assert full["cpu_baseline"]["value"] > 0 and full["cpu_baseline"]["one_thread"]["value"] > 0
+    for key in ("metric", "unit", "higher_is_better", "dtype"):
+        assert full[key] == plain[key]
+    W2, H2 = np.load(tmp_path / "full" / "W.npy"), np.load(tmp_path / "full" / "H.npy")
+    assert np.linalg.norm(W2 - W) / np.linalg.norm(W) < 1e-6 and np.linalg.norm(H2 - H) / np.linalg.norm(H) < 1e-6

@@ -19,7 +19,7 @@ import hashlib
 import numpy as np
 import pytest
 
-from golden_io import GOLDEN, rel_fro
+from golden_io import load_tall, rel_fro
 
 pytestmark = pytest.mark.gpu
 
@@ -30,8 +30,7 @@ def _case(name):
     import json
     import os
     from cnmf_amd.synthetic import iop_spectra
-    z = np.load(os.path.join(GOLDEN, f"{name}.npz"), allow_pickle=False)
-    c = {k: z[k] for k in z.files}
+    c = load_tall(name)
     c["kwargs"] = json.loads(str(c["kwargs"]))
     X = iop_spectra(int(c["n_rows"]), 81, seed=int(c["seed"]), dtype=np.float32)
     assert hashlib.sha256(np.ascontiguousarray(X).tobytes()).hexdigest() == str(c["x_sha256"])

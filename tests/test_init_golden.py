@@ -39,8 +39,8 @@ def test_tall_default_start_is_sklearns(name):
     import os
     from cnmf_amd.init import initialize_nmf
     from cnmf_amd.synthetic import iop_spectra
-    from golden_io import GOLDEN
-    z = np.load(os.path.join(GOLDEN, f"{name}.npz"), allow_pickle=False)
+    from golden_io import load_tall
+    z = load_tall(name)
     X = iop_spectra(int(z["n_rows"]), 81, seed=int(z["seed"]), dtype=np.float32)
     assert hashlib.sha256(X.tobytes()).hexdigest() == str(z["x_sha256"])
     kw = json.loads(str(z["kwargs"]))
