@@ -1,4 +1,13 @@
-// cnmf_hip.hip — MI355X (gfx950, CDNA4) kernels + C ABI for the Frobenius multiplicative update.
+// cnmf_hip.hip — the kernel library (MI355X, gfx950: kernels + C ABI).  Files of csrc/:
+//   common.hpp   constants, error reporting, element types, stamp macros
+//   host.hpp     host helpers one file calls in another (occupancy, the wave-tile plan and launch)
+//   persist.hpp  what the persistent launches share: counter map, PersistArgs, control blocks,
+//                sc1 helpers, in-launch reduction and exchange
+//   wt.hpp       wave-tile geometry and device helpers of the wave-tile kernels
+//   wt.hip       mu_iter_wt_kernel, wt_plan, launch_wt
+//   init.hip     GPU NNDSVD initialisation
+//   this file    the families not yet in a file of their own (pass, bf16, sample-lane, mf8, reductions
+//                and basis update, constrained ALS, weighted MU, the multi-iteration entry points)
 //
 // What runs per MU iteration (sklearn naming, X[N][F] samples-major):
 //
@@ -29,75 +38,12 @@
 //  * grid = persistent, sized from the occupancy query so that ceil(tiles/blocks) rounds are
 //    balanced; tiles are dealt round-robin so concurrently running workgroups stream neighbouring
 //    addresses.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <atomic>
-#include <mutex>
-#include <type_traits>
-#include <unordered_map>
-
-#include "cnmf_hip.h"
+#include "wt.hpp"
+#include "host.hpp"
 
 namespace cnmf {
 
-constexpr int TS = 64;       // samples per tile
-constexpr int NT = 256;      // threads per workgroup
-constexpr int NWAVE = NT / 64;
-constexpr int PF = 8;        // 16-byte chunks per thread held in registers for the next tile
-constexpr int NSLICE = 64;   // max slices of the deterministic cross-block reduction
-constexpr int RED_NT = 256;  // threads of the reduce / update workgroups
-constexpr double EPS32 = 1.1920928955078125e-07;  // np.finfo(np.float32).eps, SK:39
-constexpr int ALS_TAB = 16 * 16 + 16;  // constrained-ALS passive-set table: 16 masks x 4x4 + valid
-
-static thread_local char g_err[512] = "";
-
-static int set_err(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-// Diagnostic switches (A/B timing and tools/ probes) are read from the environment only in the
-// diagnostic build (-DCNMF_DIAG: python -m cnmf_amd.build --diag); the product library ignores the
-// environment, so every plan's behaviour follows from its arguments alone.
-static const char* diag_env(const char* name) {
-#ifdef CNMF_DIAG
-  return getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
-
-#define HIP_CHECK(expr)                                                                   \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess)                                                                 \
-      return set_err(CNMF_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
-  } while (0)
-
-// ------------------------------------------------------------------------------------------------
-// element conversions: X storage type -> compute type
-// ------------------------------------------------------------------------------------------------
-struct bf16_t {
-  uint16_t bits;
-};
-
-// native 16-byte vector (HIP's uint4 class type defeats SROA: the prefetch array went to scratch)
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float to_c(float v) { return v; }
-__device__ __forceinline__ double to_c(double v) { return v; }
-__device__ __forceinline__ float to_c(bf16_t v) { return __uint_as_float(((uint32_t)v.bits) << 16); }
+thread_local char g_err[512] = "";
 
 template <typename TX>
 struct Compute;
@@ -230,61 +176,6 @@ __device__ __forceinline__ T lds_at(const unsigned char* smem, uint32_t off) {
 }
 
 
-// ------------------------------------------------------------------------------------------------
-// Diagnostic phase stamps (built only with -DCNMF_STAMPS into a separate .so; never in the real
-// kernel): per wave, s_memtime deltas between the phase boundaries of every tile are summed in
-// registers and added once per wave into g_stamps[slot] (MI355X guide §7 "In-kernel stamps").
-// ------------------------------------------------------------------------------------------------
-#ifdef CNMF_STAMPS
-__device__ unsigned long long g_stamps[16];
-#define STAMP_DECL unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long st_t0 = 0;
-#define STAMP(slot)                                                                   \
-  do {                                                                                \
-    __builtin_amdgcn_sched_barrier(0);                                                \
-    unsigned long long st_t;                                                          \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_t) :: "memory");    \
-    __builtin_amdgcn_sched_barrier(0);                                                \
-    if (slot > 0) st_acc[slot] += st_t - st_t0;                                       \
-    st_t0 = st_t;                                                                     \
-  } while (0)
-#define STAMP_FLUSH                                                                   \
-  do {                                                                                \
-    if ((threadIdx.x & 63) == 0)                                                      \
-      for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&g_stamps[i_], st_acc[i_]);           \
-    if ((threadIdx.x & 63) == 0) atomicAdd(&g_stamps[8], 1ull);                       \
-  } while (0)
-// the end of a persistent bfw iteration: thread 0 of every workgroup sums the phase durations
-// (s_memtime) into g_eoi[slot]; g_eoi[15] counts the (workgroup, iteration) pairs
-__device__ unsigned long long g_eoi[16];
-// the persistent ALS resume path of workgroup 0: per slot the sum over iterations of the
-// s_memrealtime stamp (differences of the sums = summed phase durations); g_ph[15] counts
-__device__ unsigned long long g_ph[16];
-#define PH(slot)                                                                        \
-  do {                                                                                  \
-    if (threadIdx.x == 0 && blockIdx.x == 0) {                                          \
-      g_ph[slot] += __builtin_amdgcn_s_memrealtime();                                   \
-      if (slot == 0) g_ph[15] += 1ull;                                                  \
-    }                                                                                   \
-  } while (0)
-#define EOI_DECL unsigned long long eoi_t0 = 0;
-#define EOI(slot)                                                                     \
-  do {                                                                                \
-    if (threadIdx.x == 0) {                                                           \
-      unsigned long long st_t;                                                        \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_t) :: "memory");  \
-      if (slot > 0) atomicAdd(&g_eoi[slot], st_t - eoi_t0);                           \
-      else atomicAdd(&g_eoi[15], 1ull);                                               \
-      eoi_t0 = st_t;                                                                  \
-    }                                                                                 \
-  } while (0)
-#else
-#define STAMP_DECL
-#define STAMP(slot) do {} while (0)
-#define STAMP_FLUSH do {} while (0)
-#define EOI_DECL
-#define EOI(slot) do {} while (0)
-#define PH(slot) do {} while (0)
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // Phases 1+2 of a tile, shared by both pass kernels; wave-local (wave w owns samples
@@ -1781,12 +1672,6 @@ __host__ __device__ inline size_t update_lds_doubles(int F, int k, int KP) {
   return 2 * (size_t)k * F + (size_t)k * k + (size_t)KP * KP + 2 * (RED_NT / 64);
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // The basis update for KP >= 8 on v_mfma_f64_16x16x4_f64 (exact fp64; C/D layout row = g + 4·reg,
 // col = lane & 15; A/B as the f32 16x16x4 form): den = (WᵀW)·H per 16-feature block and HHᵀ = H·Hᵀ
 // with the 4 waves splitting K = F, their partials summed in fixed order.  H is staged in LDS
@@ -2148,29 +2033,7 @@ constexpr int L_H = L_RED + (RED + 15) / 16 * 16;       // H fp64 [K][F]
 constexpr int L_AB = L_H + K * F * 8;                   // AB fp64 [K][V]
 constexpr int L_FLAG = L_AB + K * V * 8;                // 4 ints
 constexpr int L_PTOTAL = L_FLAG + 16;
-constexpr int GROUP = 16;                               // workgroups per first-level group
-constexpr int MAX_GROUPS = 64;
-constexpr uint32_t XPOISON = 0xFFFFFFFFu;                // exchange flag of a failed rank
-constexpr uint64_t SPIN_TIMEOUT = 200000000ull;         // 2 s of s_memrealtime (100 MHz)
 }  // namespace sl
-
-// counter words (uint32): [0] reduce_kernel's ticket; the persistent kernel's at 128-byte strides
-static_assert(sl::MAX_GROUPS <= NSLICE, "group rows live in the reduction stage buffer");
-constexpr int CNT_GROUP0 = 32;
-constexpr int CNT_TOP = CNT_GROUP0 + 32 * sl::MAX_GROUPS;
-constexpr int CNT_FLAG = CNT_TOP + 32;
-constexpr int CNT_ERR = CNT_FLAG + 32;
-constexpr int DYN_GRP = 8;                       // workgroups per floating-tile pool
-constexpr int DYN_MAX_POOLS = sl::GROUP * sl::MAX_GROUPS / DYN_GRP;
-constexpr int CNT_POOL = CNT_ERR + 32;           // floating-tile pools [parity][pool] (32-word stride)
-constexpr int CNT_RCOL0 = CNT_POOL + 2 * DYN_MAX_POOLS * 32;          // reduce_kernel: one ticket per 64-column block
-constexpr int CNT_UPD = CNT_POOL;  // basis_update_split_kernel's ticket (the pools serve layout 3 only)
-// the wave-tile kernels' XCC table (round 6): word b = 1 + the XCC id workgroup b runs on (written at
-// the launch's start, zeroed by the launch's last combiner), in the pools' words past CNT_UPD's line
-constexpr int CNT_XCC0 = CNT_POOL + 32;
-constexpr int RED_MAX_COLS = 512;
-constexpr int CNT_WORDS = CNT_RCOL0 + RED_MAX_COLS;
-static_assert(CNT_XCC0 + sl::GROUP * sl::MAX_GROUPS <= CNT_RCOL0, "the XCC table fits the pools' words");
 
 // sHt (fp32 [84][4], rows >= 81 zero) and sHHt (fp64 [4][4]) from the fp64 H in LDS; the HHᵀ
 // arithmetic (lanes over f, fixed shuffle tree) is that of basis_update_block.
@@ -2226,78 +2089,6 @@ __device__ __forceinline__ void sl_update_basis(unsigned char* smem, int t, doub
     if (t + NT * u < K * F) sH[t + NT * u] = hn[u];
   __syncthreads();
   sl_derive_basis(smem, t);
-}
-
-struct PersistArgs {
-  const float* X;
-  float* W;
-  double* H64;       // in: the basis; out: the final basis
-  double* Ht;        // out [F][4]
-  double* HHt;       // out [4][4]
-  double* partials;  // [G][K*V] per-workgroup rows
-  double* groups;    // [NG][K*V] group rows
-  double* AB;        // [K*V]: in (apply_first) / out (the last iteration's reduced accumulators)
-  uint32_t* cnt;     // CNT_WORDS counters
-  int64_t n_tiles;
-  int n_iter;
-  int n_groups;
-  int n_static;      // DYN: tiles per workgroup with W resident; tiles n_static*G.. float (the pool)
-  double l1W, l2W, l1H, l2H;
-  int apply_first;   // first apply the pending basis update from AB (multi-GPU: AB all-reduced)
-  int apply_last;    // apply the last iteration's basis update in-launch (single GPU)
-  // MULTI (one persistent launch per rank, the all-reduce in-launch): the exchange control block
-  // (XC_* words, device memory), read only inside the exchange so that its values do not occupy
-  // SGPRs through the streaming loop
-  uint64_t* xctl;
-  // TOL (the tolerance test on the device, SK:872-884): the control block of TC_* doubles
-  double* tolctl;
-  // the wave-tile kernel's first reduction level through the XCD's L2 (round 6):
-  // a group's members (b ≡ g mod NG: one XCD under round-robin placement) store their partial rows
-  // with plain stores, kept in the L2 their combiner reads with sc1 loads — from the second iteration
-  // on, and only when the XCC table shows every member of the group on the combiner's XCC (placement
-  // is never assumed: a group spread over XCDs keeps the write-through stores)
-  int l2rows = 0;
-};
-
-// tolerance control block (doubles; TC_WSNAP holds a pointer's bits): inputs tol, it0 (global index
-// of the launch's first iteration), the capacity of the error list; in/out the error at init and the
-// previous checked error; outputs the iterations done, whether the test stopped the fit, whether
-// the stopped fit's W is in the snapshot buffer (streamed W) rather than in W itself, the count and
-// list of the checked errors (index g / 10 for the state after g iterations)
-constexpr int TC_TOL = 0, TC_IT0 = 1, TC_INIT = 2, TC_PREV = 3, TC_DONE = 4, TC_STOPPED = 5, TC_IN_SNAP = 6,
-              TC_WSNAP = 7, TC_CAP = 8, TC_NERR = 9, TC_ERRS = 16;
-static_assert(TC_TOL == CNMF_TC_TOL && TC_IT0 == CNMF_TC_IT0 && TC_INIT == CNMF_TC_INIT && TC_PREV == CNMF_TC_PREV &&
-                  TC_DONE == CNMF_TC_DONE && TC_STOPPED == CNMF_TC_STOPPED && TC_IN_SNAP == CNMF_TC_IN_SNAP &&
-                  TC_WSNAP == CNMF_TC_WSNAP && TC_CAP == CNMF_TC_CAP && TC_NERR == CNMF_TC_NERR && TC_ERRS == CNMF_TC_ERRS,
-              "tolerance control block slots = include/cnmf_hip.h");
-constexpr uint32_t FLAG_STOP = 1u << 30;  // the iteration flag of a launch the tolerance test stopped
-
-// exchange control block words: rank, world, byte offset of the flags in an exchange buffer, the
-// generation base (advanced by n_iter at the end of every launch, on the device), then the
-// world exchange-buffer pointers (this rank's own at XC_PEERS + rank)
-constexpr int XC_RANK = 0, XC_WORLD = 1, XC_FLAG_OFF = 2, XC_GEN = 3, XC_PEERS = 8;
-
-__device__ __forceinline__ double ld_sc1(const double* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_sc1(double* p, double v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// two doubles as one 16-byte sc1 store (p 16-byte aligned; the MI355X guide's table: a 16-B sc1
-// store costs about a plain one, 8-B accesses 0.54-0.70x the rate)
-__device__ __forceinline__ void st16_sc1(double* p, double v0, double v1) {
-  typedef double d2v __attribute__((ext_vector_type(2)));
-  const d2v v = d2v{v0, v1};
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-}
-
-// n / d for the W-updates of the wave-tile kernels: v_rcp_f64 + one Newton step (relative error
-// ~2^-50, far below the fp32 rounding of the new w that follows) in place of the fp64 division's
-// ~10-instruction IEEE sequence (round 5; d is a denominator >= EPS32, never denormal)
-__device__ __forceinline__ double div_nr(double n, double d) {
-  double r = __builtin_amdgcn_rcp(d);
-  r = fma(r, fma(-d, r, 1.0), r);
-  return n * r;
 }
 
 // The arguments of the bf16 wave-tile pass and of its persistent form (mu_iter_bfw_kernel).
@@ -2954,62 +2745,6 @@ __device__ __forceinline__ void sum_rows_sc1(const double* rows, int m0, int ste
   }
 }
 
-#ifdef CNMF_STAMPS
-// diagnostic timeline of the persistent kernel (s_memrealtime, 100 MHz): per iteration and
-// workgroup [0] = rows published (arrival), [1] = next iteration's basis ready (resume); per
-// iteration the top combiner's AB publish time.  Never in the product build.
-constexpr int TL_IT = 64, TL_WG = 2048;
-__device__ unsigned long long g_tl[TL_IT * TL_WG * 2];
-__device__ unsigned long long g_tl_pub[TL_IT];
-__device__ unsigned long long g_tl_x[TL_IT * 4];  // MULTI exchange: start, stored, flags seen, summed
-__device__ unsigned long long g_tl_start[TL_WG];
-__device__ unsigned int g_tl_hw[TL_WG * 2];  // HW_REG_HW_ID (cu / sh / se bits), HW_REG_XCC_ID
-#define TL(it_, slot_)                                                                          \
-  do {                                                                                          \
-    if (t == 0 && (it_) < TL_IT && b < TL_WG) g_tl[((it_) * TL_WG + b) * 2 + (slot_)] = __builtin_amdgcn_s_memrealtime(); \
-  } while (0)
-#define TL_PUB(it_) do { if (t == 0 && (it_) < TL_IT) g_tl_pub[it_] = __builtin_amdgcn_s_memrealtime(); } while (0)
-// per-level stamps of the reduction tree (round 6): [it][g][0] group g's combiner's ticket returned,
-// [1] its group row stored (vmcnt(0) + barrier); [it][TL_LVG][0] the top's ticket returned, [1] AB summed
-// and stored; and [it][wg] each workgroup's time before its partial-row stores (g_tl_pre)
-constexpr int TL_LVG = 64;
-__device__ unsigned long long g_tl_lv[TL_IT * (TL_LVG + 1) * 2];
-__device__ unsigned long long g_tl_pre[TL_IT * TL_WG];
-__device__ unsigned long long g_tl_seen[TL_IT * TL_WG];  // flag seen (non-top workgroups)
-__device__ unsigned long long g_tl_ab[TL_IT * TL_WG];    // AB in LDS (non-top workgroups)
-__device__ unsigned long long g_tl_upd[TL_IT * TL_WG];   // basis update done (before load_basis)
-#define TL_LV(it_, g_, slot_)                                                                   \
-  do {                                                                                          \
-    if (t == 0 && (it_) < TL_IT) g_tl_lv[((it_) * (TL_LVG + 1) + (g_)) * 2 + (slot_)] = __builtin_amdgcn_s_memrealtime(); \
-  } while (0)
-#define TL_PRE(it_) do { if (t == 0 && (it_) < TL_IT && b < TL_WG) g_tl_pre[(it_) * TL_WG + b] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define TL_SEEN(it_) do { if (t == 0 && (it_) < TL_IT && b < TL_WG) g_tl_seen[(it_) * TL_WG + b] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define TL_AB(it_) do { if (t == 0 && (it_) < TL_IT && b < TL_WG) g_tl_ab[(it_) * TL_WG + b] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define TL_UPD(it_) do { if (t == 0 && (it_) < TL_IT && b < TL_WG) g_tl_upd[(it_) * TL_WG + b] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define TL_X(it_, slot_) do { if (t == 0 && (it_) < TL_IT) g_tl_x[(it_) * 4 + (slot_)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define TL_START                                                                               \
-  do {                                                                                         \
-    if (t == 0 && b < TL_WG) {                                                                 \
-      g_tl_start[b] = __builtin_amdgcn_s_memrealtime();                                        \
-      unsigned hw_, xcc_;                                                                      \
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_));                        \
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_));                      \
-      g_tl_hw[2 * b] = hw_;                                                                    \
-      g_tl_hw[2 * b + 1] = xcc_;                                                               \
-    }                                                                                          \
-  } while (0)
-#else
-#define TL(it_, slot_) do {} while (0)
-#define TL_PUB(it_) do {} while (0)
-#define TL_X(it_, slot_) do {} while (0)
-#define TL_START do {} while (0)
-#define TL_LV(it_, g_, slot_) do {} while (0)
-#define TL_PRE(it_) do {} while (0)
-#define TL_SEEN(it_) do {} while (0)
-#define TL_AB(it_) do {} while (0)
-#define TL_UPD(it_) do {} while (0)
-#endif
-
 // The cross-rank all-reduce of AB (k(F+k) fp64) inside a persistent launch, run by the top
 // combiner's NT threads after the rank's own AB is in sAB (LDS) and a.AB.  Each fp64 value travels
 // as two 64-bit words {generation tag : 32-bit half}, written with system-scope atomic stores into
@@ -3470,1222 +3205,6 @@ __global__ __launch_bounds__(NT * TEAMS, TEAMS == 2 ? 1 : (PD == 1 ? 3 : 2)) voi
 }
 
 // ------------------------------------------------------------------------------------------------
-// mu_iter_wt_kernel<PD, MULTI> — the headline shape (fp32 X, F = 81, k = 4) as ONE persistent launch
-// of barrier-free WAVE tiles.
-//
-// Why: the workgroup-tile kernel above (mu_iter_sl_kernel) is issue/latency-bound, not HBM-bound —
-// with X served from L2 it runs at the same 67 µs per iteration (profiles/r02/probes/l2diag.log),
-// its waves park 46 % of their cycles on two workgroup barriers per tile and on one-deep LDS reads
-// of Hᵀ, while a plain streaming read of the same tile shape reaches 7.2 TB/s
-// (profiles/r02/probes/stream_probe*.log).
-//
-// Layout: one 4-wave workgroup per CU, one wave per SIMD (up to 512 VGPRs); every wave owns its own
-// 16-sample tiles gw + NW·i (gw = 4·blockIdx + wave, NW = 4·gridDim) and never waits for another
-// wave inside an iteration.  Lane l = (sample s = l / 4, quarter q = l % 4); q owns features
-// [21q, 21q + 21) (q = 3: 18 real features + 3 zero-Hᵀ pads).
-//  * X: PD tiles (5184 B each) in flight per wave in registers (6 × 16 B per lane, the 6th for
-//    lanes 0-3 only), staged to the wave's private LDS slot (in-order LDS: no barrier) and read
-//    back per lane along its sample row (x kept in 21 VGPRs from phase 1 to phase 3).
-//  * Hᵀ: the lane's 21 × 4 fp32 values and its HHᵀ row (fp64) live in VGPRs for the whole
-//    iteration (reloaded after each basis update) — no Hᵀ read per tile.
-//  * phase 1 (num = x·Hᵀ, SK:543): packed fp32 chains of 7 features folded into fp64 (the sl
-//    arithmetic), then a DPP reduce-scatter inside the quad: lane q ends with num[s][q].
-//  * phase 2 (SK:553-629): the fp64 update of w[s][q] against the LDS-resident W (each wave's tiles
-//    stay in LDS for the whole launch), w' gathered back to the quad by DPP broadcasts.
-//  * phase 3 (A += w'ᵀx, B += w'ᵀw', SK:639-640): packed fp32 accumulators per lane over the
-//    iteration; at its end a DPP / permlane-swap butterfly over the 16 sample lanes of each q,
-//    then the four waves' sums combined in fp64 in a fixed order -> the workgroup's partial row.
-//  * the in-launch reduction (tickets, group / top combiners, flag), the basis update in every
-//    workgroup and the optional cross-rank exchange are those of mu_iter_sl_kernel.
-// ------------------------------------------------------------------------------------------------
-namespace wt {
-constexpr int F = 81;
-constexpr int NWV = 4;                  // waves per workgroup (one per SIMD)
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-// geometry of the wave tile for k = KK components: NL = KK lanes per sample (lane l = NL·s + e),
-// TSW = 64 / NL samples per tile, NQ features per lane (e owns [NQ·e, NQ·e + NQ); the lanes past F
-// hold zero-Hᵀ pads)
-template <int KK>
-struct Geo {
-  static constexpr int K = KK, NL = KK, TSW = 64 / KK, V = F + KK, NOUT = KK * V;
-  static constexpr int NQ = (F + KK - 1) / KK;              // 21 (k = 4), 11 (k = 8)
-  static constexpr int XBW = TSW * F * 4;                   // 5184 / 2592 B of X per tile
-  static constexpr int NCHW = XBW / 16;                     // 324 / 162 chunks
-  static constexpr int PFW = (NCHW + 63) / 64;              // 6 / 3 loads per lane
-  static constexpr int LASTL = NCHW - 64 * (PFW - 1);       // lanes of the last load: 4 / 34
-  // phase 1 reads NQ features from lane e's first one, so the last sample's last lane runs OVR
-  // floats past the tile (features >= F, zero Hᵀ): they must be finite — zeros kept in the slot
-  static constexpr int OVR = (TSW - 1) * F + NQ * NL - XBW / 4;  // 3 (k = 4), 7 (k = 8)
-  static constexpr int PADB = (OVR * 4 + 15) / 16 * 16;          // 16 / 32 zero bytes
-  static constexpr int XSTR = XBW + PADB;                        // staging stride
-  static constexpr int WBW = TSW * KK * 4;                  // 256 B of W per tile
-  static constexpr int NACC = NQ * KK + KK;                 // fp32 accumulators per lane
-  // LDS carve (bytes)
-  static constexpr int L_STG = 0;                                       // [NWV][XSTR]
-  static constexpr int L_WSTG = L_STG + NWV * XSTR;                     // streamed W: [NWV][WBW]
-  static constexpr int L_RED = (L_WSTG + NWV * WBW + 15) / 16 * 16;     // [NWV][NL][NACC] fp32
-  static constexpr int L_H = (L_RED + NWV * NL * NACC * 4 + 15) / 16 * 16;  // H fp64 [K][F]
-  static constexpr int L_AB = L_H + KK * F * 8;                         // AB fp64 [K][V] (+ the loss)
-  static constexpr int L_HT = L_AB + (NOUT + 2) * 8;                    // Hᵀ fp32 [NL·NQ][K]
-  static constexpr int L_HHT = L_HT + NL * NQ * KK * 4;                 // HHᵀ fp64 [K][K]
-  static constexpr int L_FLAG = L_HHT + KK * KK * 8;                    // 8 ints
-  static constexpr int L_LOSS = L_FLAG + 32;                            // [NWV] wave loss sums, init, prev
-  static constexpr int L_WRES = (L_LOSS + 8 * 8 + 15) / 16 * 16;        // [NWV][nbt_max][WBW]
-  static_assert(NCHW * 16 == XBW && XBW % 16 == 0, "tiles are whole 16-byte chunks");
-  static_assert(OVR >= 0 && PADB / 4 <= 64, "one zero float per lane covers the overrun");
-  static_assert(NOUT <= 3 * NT, "three accumulator outputs per thread at most");
-  static_assert(NOUT * 8 >= NWV * 64 * 4, "the prologue's dummy stores stay inside the partial row");
-};
-
-template <int CTRL>
-__device__ __forceinline__ double dpp64(double v) {
-  const long long u = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(u & 0xFFFFFFFFll), CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(u >> 32), CTRL, 0xF, 0xF, true);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-// the value of lane l ^ 16 / l ^ 32 (v_permlane16/32_swap: lanes 32-63 of the first operand trade
-// with lanes 0-31 of the second, resp. the odd 16-lane rows of the first with the even rows of the
-// second; with both operands v, the first result holds l ^ 32 in the upper half / l ^ 16 in the odd
-// rows, the second in the lower half / the even rows)
-__device__ __forceinline__ double lane_xor16(double v) {
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-  const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-  const bool odd = (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) & 16) != 0;
-  return __hiloint2double(odd ? (int)b[0] : (int)b[1], odd ? (int)a[0] : (int)a[1]);
-}
-__device__ __forceinline__ double lane_xor32(double v) {
-  const int lo = __double2loint(v), hi = __double2hiint(v);
-  const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-  const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-  const bool up = (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) & 32) != 0;
-  return __hiloint2double(up ? (int)b[0] : (int)b[1], up ? (int)a[0] : (int)a[1]);
-}
-
-// v summed over the lanes l' ≡ l (mod NL) of the wave (every lane gets its class's sum)
-template <int NL>
-__device__ __forceinline__ float sum_over_samples(float v) {
-  if (NL == 4) v += dppf<0x124>(v);  // row_ror:4
-  v += dppf<0x128>(v);               // row_ror:8
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = __uint_as_float(r[0]) + __uint_as_float(r[1]);  // + lane ^ 16
-  auto r2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r2[0]) + __uint_as_float(r2[1]);  // + lane ^ 32
-}
-
-// Reduce-scatter of N per-lane floats over the lanes l' ≡ l (mod NL) (round 6): two permlane swap
-// levels halve the values each (permlane32_swap(x, y): the lower half-wave ends with x's pair sum,
-// the upper with y's; permlane16_swap likewise for even / odd 16-lane rows) — one swap and one add
-// per PAIR of values, where the all-reduce form spends two of each per value — and the samples
-// left inside a row are summed by DPP row rotations (ror 4 and 8 at NL = 4, ror 8 at NL = 8).
-// On return v[0 .. N/4) of every lane of row r = l / 16 hold the totals of values
-// j0 + [0, N/4) with j0 = (N/2)·(r >> 1) + (N/4)·(r & 1) (the same in the row's lanes of one class).
-template <int NL, int N>
-__device__ __forceinline__ void scatter_over_samples(float (&v)[N]) {
-  static_assert(N % 4 == 0 && (NL == 4 || NL == 8), "four quarters of the values, 4 or 8 lanes per sample");
-#pragma unroll
-  for (int j = 0; j < N / 2; ++j) {
-    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[j]), __float_as_uint(v[j + N / 2]), false, false);
-    v[j] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  }
-#pragma unroll
-  for (int j = 0; j < N / 4; ++j) {
-    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[j]), __float_as_uint(v[j + N / 4]), false, false);
-    v[j] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  }
-#pragma unroll
-  for (int j = 0; j < N / 4; ++j) {
-    if (NL == 4) v[j] += dppf<0x124>(v[j]);  // row_ror:4
-    v[j] += dppf<0x128>(v[j]);               // row_ror:8
-  }
-}
-
-// v summed over the 16 lanes of its row (every lane gets the row's sum)
-__device__ __forceinline__ float sum_over_row16(float v) {
-  v += dppf<0x128>(v);  // row_ror:8
-  v += dppf<0x124>(v);  // row_ror:4
-  v += dppf<0x122>(v);  // row_ror:2
-  return v + dppf<0x121>(v);  // row_ror:1
-}
-
-// The X (and streamed W) prefetch lives in AGPRs and never touches a VGPR: inline-asm loads into
-// AGPR tuples, an asm wait naming them "+a", and asm ds_write_b128 straight from the AGPRs into
-// the staging slot (cdna_hip_programming.md §5.7 item 1, form ii).  Two reasons: (1) hipcc's own
-// counted waits for compiler-issued loads degrade to vmcnt(0) at this loop's header (one tile in
-// flight instead of PD), and (2) under this kernel's VGPR pressure hipcc parks VGPR-resident
-// prefetch registers in AGPRs, copying them before the data has landed.  VMEM operations retire
-// in issue order, so before staging set k, vmcnt(L·(PD-1)) (L loads per set) leaves exactly the
-// PD-1 younger sets in flight; compiler-issued memory operations in between only make it stricter.
-#ifdef CNMF_X_PLAIN
-#define WT_LD "global_load_dwordx4 %0, %1, off"
-#else
-#define WT_LD "global_load_dwordx4 %0, %1, off nt"
-#endif
-__device__ __forceinline__ void ld16(u32x4& r, const unsigned char* p) {
-  asm volatile(WT_LD : "=a"(r) : "v"(p) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_n() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-template <int N, int C>
-__device__ __forceinline__ void wait_set(u32x4 (&pf)[C]) {
-  static_assert(N >= 0 && N <= 63, "s_waitcnt vmcnt is a 6-bit field: a deeper prefetch cannot be counted");
-  if constexpr (C == 7)
-    asm volatile("s_waitcnt vmcnt(%7)"
-                 : "+a"(pf[0]), "+a"(pf[1]), "+a"(pf[2]), "+a"(pf[3]), "+a"(pf[4]), "+a"(pf[5]), "+a"(pf[6])
-                 : "n"(N) : "memory");
-  else if constexpr (C == 6)
-    asm volatile("s_waitcnt vmcnt(%6)"
-                 : "+a"(pf[0]), "+a"(pf[1]), "+a"(pf[2]), "+a"(pf[3]), "+a"(pf[4]), "+a"(pf[5])
-                 : "n"(N) : "memory");
-  else if constexpr (C == 4)
-    asm volatile("s_waitcnt vmcnt(%4)" : "+a"(pf[0]), "+a"(pf[1]), "+a"(pf[2]), "+a"(pf[3]) : "n"(N) : "memory");
-  else if constexpr (C == 3)
-    asm volatile("s_waitcnt vmcnt(%3)" : "+a"(pf[0]), "+a"(pf[1]), "+a"(pf[2]) : "n"(N) : "memory");
-  else
-    static_assert(C == 3 || C == 4 || C == 6 || C == 7, "prefetch set size");
-}
-template <int OFF>
-__device__ __forceinline__ void st16(unsigned addr, const u32x4& v) {
-  asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(addr), "a"(v), "i"(OFF) : "memory");
-}
-template <int OFF, int U>
-__device__ __forceinline__ void stage_rec(unsigned addr, const u32x4* pf) {
-  st16<OFF>(addr, pf[0]);
-  if constexpr (U > 1) stage_rec<OFF + 1024, U - 1>(addr, pf + 1);
-}
-}  // namespace wt
-
-// sum of `cnt` rows (m0, m0 + step, ...) of NOUT doubles each, in row order, sc1 loads (the NOUT-
-// generic form of sum_rows_sc1: up to three outputs per thread, their row batches in flight together)
-template <int NOUT>
-__device__ __forceinline__ void sum_rows_n(const double* rows, int m0, int step, int cnt, double* lds_out,
-                                           double* g_out, int t) {
-  constexpr int U = (NOUT + NT - 1) / NT;
-  constexpr int RB = U == 1 ? 16 : (U == 2 ? 16 : 8);
-  int o[U];
-  double v[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    o[u] = t + NT * u < NOUT ? t + NT * u : t;
-    v[u] = 0.0;
-  }
-  for (int m = 0; m < cnt; m += RB) {
-    double x[RB][U];
-#pragma unroll
-    for (int r = 0; r < RB; ++r) {
-      const int row = m0 + min(m + r, cnt - 1) * step;
-#pragma unroll
-      for (int u = 0; u < U; ++u) x[r][u] = ld_sc1(rows + (size_t)row * NOUT + o[u]);
-    }
-#pragma unroll
-    for (int r = 0; r < RB; ++r)
-#pragma unroll
-      for (int u = 0; u < U; ++u) v[u] += m + r < cnt ? x[r][u] : 0.0;
-  }
-#pragma unroll
-  for (int u = 0; u < U; ++u)
-    if (t + NT * u < NOUT) {
-      if (lds_out) lds_out[o[u]] = v[u];
-      st_sc1(g_out + o[u], v[u]);
-    }
-}
-
-// 16-byte agent-scope (sc1) loads and stores: the valid-forms table's first row allows 16-B sc1
-// stores and loads on both sides of a hand-off (MI355X_MICROARCH.md); one instruction per two doubles
-// where sum_rows_n moved 8 bytes per lane (round 6: the guide's 8-B accesses run at 0.54-0.70x the
-// 16-B rate, and the tail's combines were latency-bound on those loads, profiles/r06/tree/)
-__device__ __forceinline__ void ld16_sc1(u32x4& r, const double* p) {
-  asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(r) : "v"(p) : "memory");
-}
-__device__ __forceinline__ void st16_sc1v(double* p, double v0, double v1) {
-  const u32x4 v = u32x4{(unsigned)__double2loint(v0), (unsigned)__double2hiint(v0), (unsigned)__double2loint(v1),
-                        (unsigned)__double2hiint(v1)};
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-}
-__device__ __forceinline__ void st16_plain(double* p, double v0, double v1) {
-  const u32x4 v = u32x4{(unsigned)__double2loint(v0), (unsigned)__double2hiint(v0), (unsigned)__double2loint(v1),
-                        (unsigned)__double2hiint(v1)};
-  asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(p), "v"(v) : "memory");
-}
-__device__ __forceinline__ double lo_d(const u32x4& r) { return __hiloint2double((int)r[1], (int)r[0]); }
-__device__ __forceinline__ double hi_d(const u32x4& r) { return __hiloint2double((int)r[3], (int)r[2]); }
-template <int N>
-__device__ __forceinline__ void wait8(u32x4 (&x)[8]) {
-  asm volatile("s_waitcnt vmcnt(%8)"
-               : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7])
-               : "n"(N) : "memory");
-}
-// sum_rows_n for an even NOUT with 16-byte sc1 loads: thread t owns the chunks (doubles 2c, 2c + 1)
-// c = t (and c = t + NT when NOUT / 2 > NT: k = 8) of every row and adds the rows in row order
-// (0.0 + r0 + r1 + ...: the same operations, the same bits as sum_rows_n); 16 loads in flight per
-// batch (one chunk: 16 rows, two waits of 8 in issue order; two chunks: 8 rows each); the result
-// goes to lds_out (optional) and, with 16-byte sc1 stores, to g_out
-template <int NOUT>
-__device__ __forceinline__ void sum_rows_v(const double* rows, int m0, int step, int cnt, double* lds_out,
-                                           double* g_out, int t) {
-  static_assert(NOUT % 2 == 0 && NOUT / 2 <= 2 * NT, "one or two 16-byte chunks per thread");
-  constexpr int NCH = NOUT / 2, UC = NCH > NT ? 2 : 1;
-  const int c0 = t < NCH ? t : NCH - 1;                    // threads past the row re-load its last chunk
-  const int c1 = t + NT < NCH ? t + NT : NCH - 1;          // (never stored)
-  double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
-  if constexpr (UC == 1) {
-    for (int m = 0; m < cnt; m += 16) {
-      u32x4 xa[8], xb[8];
-#pragma unroll
-      for (int r = 0; r < 8; ++r) ld16_sc1(xa[r], rows + (size_t)(m0 + min(m + r, cnt - 1) * step) * NOUT + 2 * c0);
-#pragma unroll
-      for (int r = 0; r < 8; ++r) ld16_sc1(xb[r], rows + (size_t)(m0 + min(m + 8 + r, cnt - 1) * step) * NOUT + 2 * c0);
-      wait8<8>(xa);
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        v0 += m + r < cnt ? lo_d(xa[r]) : 0.0;
-        v1 += m + r < cnt ? hi_d(xa[r]) : 0.0;
-      }
-      wait8<0>(xb);
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        v0 += m + 8 + r < cnt ? lo_d(xb[r]) : 0.0;
-        v1 += m + 8 + r < cnt ? hi_d(xb[r]) : 0.0;
-      }
-    }
-  } else {
-    for (int m = 0; m < cnt; m += 8) {
-      u32x4 xa[8], xb[8];
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const size_t row = (size_t)(m0 + min(m + r, cnt - 1) * step) * NOUT;
-        ld16_sc1(xa[r], rows + row + 2 * c0);
-        ld16_sc1(xb[r], rows + row + 2 * c1);
-      }
-      wait8<0>(xa);  // (both arrays' loads are interleaved: wait for all)
-      wait8<0>(xb);
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        v0 += m + r < cnt ? lo_d(xa[r]) : 0.0;
-        v1 += m + r < cnt ? hi_d(xa[r]) : 0.0;
-        v2 += m + r < cnt ? lo_d(xb[r]) : 0.0;
-        v3 += m + r < cnt ? hi_d(xb[r]) : 0.0;
-      }
-    }
-  }
-  if (t < NCH) {
-    if (lds_out) {
-      lds_out[2 * t] = v0;
-      lds_out[2 * t + 1] = v1;
-    }
-    st16_sc1v(g_out + 2 * t, v0, v1);
-  }
-  if (UC == 2 && t + NT < NCH) {
-    if (lds_out) {
-      lds_out[2 * (t + NT)] = v2;
-      lds_out[2 * (t + NT) + 1] = v3;
-    }
-    st16_sc1v(g_out + 2 * (t + NT), v2, v3);
-  }
-}
-
-// the cross-rank all-reduce of AB inside a persistent launch (xchg_allreduce_ab's protocol,
-// generic in the accumulator count NOUT; slot stride 2·NOUT words)
-template <int NOUT>
-__device__ __forceinline__ void xchg_allreduce_n(uint64_t* xctl, double* AB, double* sAB, uint32_t* err, int it, int t) {
-  constexpr int U = (NOUT + NT - 1) / NT;
-  const int xrank = (int)__hip_atomic_load(xctl + XC_RANK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const int xworld = (int)__hip_atomic_load(xctl + XC_WORLD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const uint32_t gen =
-      (uint32_t)__hip_atomic_load(xctl + XC_GEN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + (uint32_t)it + 1u;
-  auto peer = [&](int r) {
-    return reinterpret_cast<uint64_t*>(__hip_atomic_load(xctl + XC_PEERS + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-  };
-  TL_X(it, 0);
-  const size_t slot = 2 * (size_t)NOUT;
-  const size_t par = (size_t)(gen & 1u) * xworld * slot;
-  int o[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) o[u] = t + NT * u < NOUT ? t + NT * u : t;
-  {
-    const bool bad = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
-    const uint64_t tag = (uint64_t)(bad ? sl::XPOISON : gen) << 32;
-    for (int pr = 0; pr < xworld; ++pr) {
-      uint64_t* dst = peer(pr) + par + (size_t)xrank * slot;
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (t + NT * u < NOUT) {
-          const uint64_t bv = (uint64_t)__double_as_longlong(sAB[o[u]]);
-          __hip_atomic_store(dst + 2 * o[u], tag | (bv & 0xFFFFFFFFull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          __hip_atomic_store(dst + 2 * o[u] + 1, tag | (bv >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-  }
-  TL_X(it, 1);
-  const uint64_t* mine = peer(xrank) + par;
-  double v[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) v[u] = 0.0;
-  constexpr int QB = 4;  // ranks polled per round (their loads in flight together)
-  for (int q0 = 0; q0 < xworld; q0 += QB) {
-    uint64_t w[QB][2 * U];
-    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-    while (true) {
-      const uint32_t ev = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // same batch
-#pragma unroll
-      for (int j = 0; j < QB; ++j) {
-        const uint64_t* src = mine + (size_t)min(q0 + j, xworld - 1) * slot;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          w[j][2 * u] = __hip_atomic_load(src + 2 * o[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          w[j][2 * u + 1] = __hip_atomic_load(src + 2 * o[u] + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
-      bool ok = true, poison = false;
-#pragma unroll
-      for (int j = 0; j < QB; ++j)
-#pragma unroll
-        for (int m = 0; m < 2 * U; ++m) {
-          const uint32_t tg = (uint32_t)(w[j][m] >> 32);
-          ok = ok && tg == gen;
-          poison = poison || tg == sl::XPOISON;
-        }
-      if (ok) break;
-      if (poison) {
-        __hip_atomic_store(err, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-      if (ev != 0u) break;
-      if (__builtin_amdgcn_s_memrealtime() - t0 > sl::SPIN_TIMEOUT) {
-        __hip_atomic_store(err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-#pragma unroll
-    for (int j = 0; j < QB; ++j)
-      if (q0 + j < xworld)  // rank order
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-          v[u] += __longlong_as_double((long long)((w[j][2 * u + 1] << 32) | (w[j][2 * u] & 0xFFFFFFFFull)));
-  }
-  TL_X(it, 2);
-#pragma unroll
-  for (int u = 0; u < U; ++u)
-    if (t + NT * u < NOUT) {
-      sAB[o[u]] = v[u];
-      st_sc1(AB + o[u], v[u]);
-    }
-  TL_X(it, 3);
-}
-
-// HHᵀ (fp64) from the fp64 H in LDS: NT / K² consecutive threads per entry (16 at k = 4: one DPP row;
-// 4 at k = 8: a quad), each a strided part of the F products, then a fixed DPP butterfly over the
-// group (xor 1, xor 2 by quad_perm; at 16 the half-row and row mirrors) — register moves where the
-// round-5 xor tree went through the LDS crossbar (ds_bpermute, a dependent round trip per level).
-// Every entry takes the same operations in the same order, and HHᵀ[j][m] / HHᵀ[m][j] are the same
-// products, so it stays exactly symmetric.  Caller synchronises.
-template <int KK, class G = wt::Geo<KK>>
-__device__ __forceinline__ void wt_hht(unsigned char* smem, int t) {
-  const double* sH = reinterpret_cast<const double*>(smem + G::L_H);
-  double* sHHt = reinterpret_cast<double*>(smem + G::L_HHT);
-  constexpr int NE = KK * KK, TPE = NT / NE;
-  static_assert(TPE * NE == NT && (TPE == 4 || TPE == 16), "threads per HHᵀ entry: a quad or a DPP row");
-  const int en = t / TPE, part = t - en * TPE;
-  const int j = en / KK, m = en - (en / KK) * KK;
-  // the strided products with a compile-time trip count: every LDS read of the row pair issued
-  // before the first FMA (a runtime loop waited on each iteration's reads in turn)
-  constexpr int NF = (wt::F + TPE - 1) / TPE;
-  double hj[NF], hm[NF];
-#pragma unroll
-  for (int i = 0; i < NF; ++i) {
-    const int f = part + TPE * i < wt::F ? part + TPE * i : wt::F - 1;
-    hj[i] = sH[j * wt::F + f];
-    hm[i] = sH[m * wt::F + f];
-  }
-  double v = 0.0;
-#pragma unroll
-  for (int i = 0; i < NF; ++i)
-    if (part + TPE * i < wt::F) v = fma(hj[i], hm[i], v);
-  v += wt::dpp64<0xB1>(v);  // quad_perm [1,0,3,2]
-  v += wt::dpp64<0x4E>(v);  // quad_perm [2,3,0,1]
-  if constexpr (TPE == 16) {
-    v += wt::dpp64<0x141>(v);  // row_half_mirror: the other quad of the half-row
-    v += wt::dpp64<0x140>(v);  // row_mirror: the other half-row
-  }
-  if (part == 0) sHHt[en] = v;
-}
-// Hᵀ (fp32, the lanes' feature blocks, rows >= F zero) and HHᵀ from the fp64 H in LDS — sl_derive_basis
-// for k = KK
-template <int KK, class G = wt::Geo<KK>>
-__device__ __forceinline__ void wt_derive_basis(unsigned char* smem, int t) {
-  const double* sH = reinterpret_cast<const double*>(smem + G::L_H);
-  float* sHt = reinterpret_cast<float*>(smem + G::L_HT);
-  for (int e = t; e < G::NL * G::NQ * KK; e += NT) {
-    const int f = e / KK;
-    const int j = e - f * KK;
-    sHt[e] = f < wt::F ? (float)sH[j * wt::F + f] : 0.f;
-  }
-  wt_hht<KK, G>(smem, t);
-  __syncthreads();
-}
-// H <- H·(WᵀX / ((WᵀW)·H (+l1)(+l2·H))) on the fp64 H in LDS from AB in LDS (SK:634-728) —
-// sl_update_basis for k = KK.  Round 6: the quotient as div_nr (v_rcp_f64 + one Newton step, the
-// W-update's arithmetic) and the new Hᵀ written with the new H (its pad rows stay zero), then HHᵀ
-template <int KK, class G = wt::Geo<KK>>
-__device__ __forceinline__ void wt_update_basis(unsigned char* smem, int t, double l1, double l2) {
-  constexpr int KF = KK * wt::F;
-  constexpr int U = (KF + NT - 1) / NT;
-  double* sH = reinterpret_cast<double*>(smem + G::L_H);
-  float* sHt = reinterpret_cast<float*>(smem + G::L_HT);
-  const double* sAB = reinterpret_cast<const double*>(smem + G::L_AB);
-  double hn[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const int e = t + NT * u;
-    hn[u] = 0.0;
-    if (e < KF) {
-      const int j = e / wt::F;
-      const int f = e - j * wt::F;
-      const double h = sH[e];
-      const double num = sAB[j * G::V + f];                                      // (WᵀX)[j][f], SK:639
-      double den = 0.0;                                                          // ((WᵀW)·H)[j][f], SK:640
-      for (int m = 0; m < KK; ++m) den = fma(sAB[j * G::V + wt::F + m], sH[m * wt::F + f], den);
-      if (l1 > 0.0) den += l1;                                                   // SK:702-703
-      if (l2 > 0.0) den = den + l2 * h;                                          // SK:704-705
-      if (den == 0.0) den = EPS32;                                               // SK:706
-      hn[u] = h * div_nr(num, den);                                              // SK:722-726
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const int e = t + NT * u;
-    if (e < KF) {
-      const int j = e / wt::F;
-      const int f = e - j * wt::F;
-      sH[e] = hn[u];
-      sHt[f * KK + j] = (float)hn[u];
-    }
-  }
-  // Hᵀ's pad rows (features >= F, read by the lanes past F): zero (a launch that starts with the
-  // pending update, apply_first, has not run wt_derive_basis)
-  for (int e = wt::F * KK + t; e < G::NL * G::NQ * KK; e += NT) sHt[e] = 0.f;
-  __syncthreads();
-  wt_hht<KK, G>(smem, t);
-  __syncthreads();
-}
-
-// The round-5 forms of wt_derive_basis / wt_update_basis (xor-shuffle HHᵀ tree, IEEE division), kept
-// for k = 8: the round-6 end of iteration measured 3.5 % slower on cfg3's k = 8 shard (the streaming
-// body's schedule, not the tail; profiles/r06/tree/), so that kernel keeps the round-5 tail.
-// Hᵀ (fp32, the lanes' feature blocks, rows >= F zero) and HHᵀ (fp64; lanes over f, fixed shuffle
-// tree) from the fp64 H in LDS — sl_derive_basis for k = KK
-template <int KK, class G = wt::Geo<KK>>
-__device__ __forceinline__ void wt_derive_basis_r5(unsigned char* smem, int t) {
-  const double* sH = reinterpret_cast<const double*>(smem + G::L_H);
-  float* sHt = reinterpret_cast<float*>(smem + G::L_HT);
-  double* sHHt = reinterpret_cast<double*>(smem + G::L_HHT);
-  for (int e = t; e < G::NL * G::NQ * KK; e += NT) {
-    const int f = e / KK;
-    const int j = e - f * KK;
-    sHt[e] = f < wt::F ? (float)sH[j * wt::F + f] : 0.f;
-  }
-  // HHᵀ: NT / K² consecutive threads per entry (16 at k = 4, 4 at k = 8), each a strided part of the
-  // F products, then a fixed xor tree over the group (every entry in the same order; HHᵀ[j][m] and
-  // HHᵀ[m][j] are the same products, so it stays exactly symmetric)
-  constexpr int NE = KK * KK, TPE = NT / NE;
-  static_assert(TPE * NE == NT && (TPE & (TPE - 1)) == 0, "threads per HHᵀ entry: a power of two");
-  const int en = t / TPE, part = t - en * TPE;
-  const int j = en / KK, m = en - (en / KK) * KK;
-  double v = 0.0;
-  for (int f = part; f < wt::F; f += TPE) v = fma(sH[j * wt::F + f], sH[m * wt::F + f], v);
-#pragma unroll
-  for (int o = TPE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if (part == 0) sHHt[en] = v;
-  __syncthreads();
-}
-// H <- H·(WᵀX / ((WᵀW)·H (+l1)(+l2·H))) on the fp64 H in LDS from AB in LDS (SK:634-728) —
-// sl_update_basis for k = KK
-template <int KK, class G = wt::Geo<KK>>
-__device__ __forceinline__ void wt_update_basis_r5(unsigned char* smem, int t, double l1, double l2) {
-  constexpr int KF = KK * wt::F;
-  constexpr int U = (KF + NT - 1) / NT;
-  double* sH = reinterpret_cast<double*>(smem + G::L_H);
-  const double* sAB = reinterpret_cast<const double*>(smem + G::L_AB);
-  double hn[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const int e = t + NT * u;
-    hn[u] = 0.0;
-    if (e < KF) {
-      const int j = e / wt::F;
-      const int f = e - j * wt::F;
-      const double h = sH[e];
-      const double num = sAB[j * G::V + f];                                      // (WᵀX)[j][f], SK:639
-      double den = 0.0;                                                          // ((WᵀW)·H)[j][f], SK:640
-      for (int m = 0; m < KK; ++m) den = fma(sAB[j * G::V + wt::F + m], sH[m * wt::F + f], den);
-      if (l1 > 0.0) den += l1;                                                   // SK:702-703
-      if (l2 > 0.0) den = den + l2 * h;                                          // SK:704-705
-      if (den == 0.0) den = EPS32;                                               // SK:706
-      hn[u] = h * (num / den);                                                   // SK:722-726
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int u = 0; u < U; ++u)
-    if (t + NT * u < KF) sH[t + NT * u] = hn[u];
-  __syncthreads();
-  wt_derive_basis_r5<KK, G>(smem, t);
-}
-
-// TOL: the tolerance test of SK:872-884 on the device.  In iteration g + 1 (g = it0 + it, g % 10 ==
-// 0) each lane also accumulates ‖x − w·H‖² of the state AFTER g iterations (x, the old w and H are
-// all in registers then: fp32 residual per element, fp64 sums per tile), carried as one more
-// column of the partial rows (NOUT + 1) and reduced / exchanged with [WᵀX | WᵀW]; the top combiner
-// applies the relative-decrease test.  On a stop it publishes the flag with FLAG_STOP and every
-// workgroup leaves with the state after g iterations: H (not updated), W as it was before this
-// iteration's update — written to W itself in the loss iterations when W is resident in LDS, else to
-// the snapshot buffer (TC_WSNAP; the host copies it) — so n_iter = g as in sklearn.
-template <int KK, bool WRES, int PD, bool MULTI = false, bool TOL = false>
-__global__ __launch_bounds__(NT, 1) void mu_iter_wt_kernel(PersistArgs a) {
-  using namespace wt;
-  using G_ = Geo<KK>;
-  constexpr int NL = G_::NL, TSW = G_::TSW, NQ = G_::NQ, V = G_::V, NOUT = G_::NOUT;
-  constexpr int NOUTT = NOUT + (TOL ? 1 : 0);  // partial-row width: + the loss of the checked state
-  // row stride of the partial / group rows and AB: even, so that every row is 16-byte chunks (round 6:
-  // 16-byte sc1 hand-offs; TOL's odd NOUTT + a zero pad — cnmf_mu_fit_tol's rows of k(F+k) + 2)
-  // k = 8 keeps the round-5 tail (8-byte hand-offs, the round-5 basis update; see wt_update_basis_r5)
-  constexpr bool R6 = KK == 4;
-  constexpr int RS = R6 ? (NOUTT + 1) & ~1 : NOUTT;
-  constexpr int XBW = G_::XBW, XSTR = G_::XSTR, WBW = G_::WBW, NACC = G_::NACC;
-  constexpr int PFW = G_::PFW, LASTL = G_::LASTL;
-  constexpr int PFS = PFW + (WRES ? 0 : 1);  // loads per prefetch set (+ the W tile when streamed)
-  // stores per body: W streamed — its W tile, and TOL's snapshot of the checked state's W (a resident
-  // W keeps that snapshot in LDS: no store, so the counted waits are the plain kernel's)
-  constexpr int NSTB = (WRES ? 0 : 1) + (TOL && !WRES ? 1 : 0);
-  constexpr int KP = KK / 2;                 // component pairs
-  // the PD prefetch sets live in AGPRs (4 per load) next to the kernel's own registers: past a
-  // budget the allocator spills them to scratch right behind their loads, i.e. before the data has
-  // landed, and the staged tiles are stale (k = 8 streamed W at PD = 6: 96 AGPRs, all-NaN W at 2.5x
-  // the time).  tools/kcheck.py checks the built library for exactly that; the
-  // depths measured clean are allowed here (k = 8: PD <= 5, 80 AGPRs; k = 4: PD <= 4, 96)
-  static_assert(4 * PD * PFS <= (KK == 8 ? 80 : 96), "prefetch depth past the measured AGPR budget");
-  static_assert(PFS * (PD - 1) + NSTB * PD <= 63, "the counted wait's vmcnt is a 6-bit field");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int t = threadIdx.x;
-  const int l = t & 63;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int s = l / NL, e = l % NL;
-  const int b = blockIdx.x;
-  const int G = gridDim.x;
-  const int NW = NWV * G;
-  const int gw = NWV * b + w;
-  const int NG = a.n_groups;
-  const int g = b % NG;
-  const int gs = (G - g + NG - 1) / NG;
-  const unsigned char* Xb = reinterpret_cast<const unsigned char*>(a.X);
-  unsigned char* Wb = reinterpret_cast<unsigned char*>(a.W);
-  const int nbt = (int)((a.n_tiles - gw + NW - 1) / NW);  // this wave's tiles per iteration
-  const int nbt_max = (int)((a.n_tiles + NW - 1) / NW);
-  unsigned char* stg = smem + G_::L_STG + w * XSTR;
-  unsigned char* wstg = smem + G_::L_WSTG + w * WBW;  // streamed W: this wave's current tile
-  // W streamed: its first nres tiles per wave resident all the same (the LDS the plan has left; round
-  // 5): their W loads re-load an X chunk (the counted waits see the same loads) and their stores go
-  // to the dummy word (the same stores), the rest streams
-  const int nres = WRES ? 0 : __builtin_amdgcn_readfirstlane(a.n_static);
-  float* wres = reinterpret_cast<float*>(smem + G_::L_WRES + (size_t)w * (WRES ? nbt_max : nres) * WBW);  // [i][TSW][K]
-  float* red = reinterpret_cast<float*>(smem + G_::L_RED);
-  double* sH = reinterpret_cast<double*>(smem + G_::L_H);
-  double* sAB = reinterpret_cast<double*>(smem + G_::L_AB);
-  int* sFlag = reinterpret_cast<int*>(smem + G_::L_FLAG);
-  double* sLoss = reinterpret_cast<double*>(smem + G_::L_LOSS);
-  // TOL: the launch's first global iteration, the snapshot buffer (streamed W)
-  const int it0 = TOL ? (int)ld_sc1(a.tolctl + TC_IT0) : 0;
-  // TOL: every workgroup tracks the test's error at init and previous error itself (sLoss[4], [5]),
-  // so the decision of the iteration's top combiner reads no state another workgroup wrote
-  const double tolv = TOL ? ld_sc1(a.tolctl + TC_TOL) : 0.0;
-  if (TOL && t == 0) {
-    sLoss[4] = ld_sc1(a.tolctl + TC_INIT);
-    sLoss[5] = ld_sc1(a.tolctl + TC_PREV);
-  }
-  float* wsnap = (TOL && !WRES)
-                     ? reinterpret_cast<float*>(__double_as_longlong(ld_sc1(a.tolctl + TC_WSNAP)))
-                     : nullptr;
-  // TOL with W resident: the W of the state a loss iteration checks, this wave's tiles [i][TSW][K],
-  // after the four waves' resident W (the host sizes the LDS for both)
-  float* wsnapl = (TOL && WRES) ? reinterpret_cast<float*>(smem + G_::L_WRES + (size_t)(NWV + w) * nbt_max * WBW)
-                                : nullptr;
-  double lossacc = 0.0;  // this lane's ‖x − w·H‖² over the iteration's tiles (loss iterations)
-  uint32_t* cnt_group = a.cnt + CNT_GROUP0 + 32 * g;
-  uint32_t* cnt_top = a.cnt + CNT_TOP;
-  uint32_t* flag = a.cnt + CNT_FLAG;
-  uint32_t* err = a.cnt + CNT_ERR;
-
-  // ---- the basis for the first iteration, the staging pads, this wave's W tiles (W resident)
-  const bool l2rows = R6 && a.l2rows != 0;
-  if (t == 0) {  // the XCC this workgroup runs on, into the table (read once, after iteration 0)
-    unsigned xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    sFlag[4] = 0;  // partial rows write-through until the group's placement has been checked
-    sFlag[5] = (int)(xcc & 0xFu) + 1;
-    if (l2rows) __hip_atomic_store(a.cnt + CNT_XCC0 + b, (xcc & 0xFu) + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  for (int i = t; i < KK * F; i += NT) sH[i] = a.H64[i];
-  if (a.apply_first)
-    for (int i = t; i < NOUT; i += NT) sAB[i] = a.AB[i];
-  if (l < G_::PADB / 4) reinterpret_cast<float*>(stg + XBW)[l] = 0.f;
-  {
-    const int nw = WRES ? nbt : min(nres, nbt);
-    for (int c = l; c < nw * (WBW / 16); c += 64) {
-      const int i = c / (WBW / 16), ch = c - i * (WBW / 16);
-      *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned char*>(wres) + i * WBW + 16 * ch) =
-          *reinterpret_cast<const u32x4*>(Wb + (size_t)(gw + (int64_t)NW * i) * WBW + 16 * ch);
-    }
-  }
-  __syncthreads();
-  if (a.apply_first) {
-    if constexpr (R6) wt_update_basis<KK>(smem, t, a.l1H, a.l2H);
-    else wt_update_basis_r5<KK>(smem, t, a.l1H, a.l2H);
-  } else {
-    if constexpr (R6) wt_derive_basis<KK>(smem, t);
-    else wt_derive_basis_r5<KK>(smem, t);
-  }
-
-  // the lane's Hᵀ (fp32 component pairs of each of its NQ features) and HHᵀ row e
-  f2 hp[NQ][KP];
-  double hh[KK];
-  f2 hh32[KP];  // k = 8: the HHᵀ row in fp32 pairs for the denominator
-  auto load_basis = [&]() {
-    const float* sHt = reinterpret_cast<const float*>(smem + G_::L_HT);
-    const double* sHHt = reinterpret_cast<const double*>(smem + G_::L_HHT);
-#pragma unroll
-    for (int c = 0; c < NQ; ++c)
-#pragma unroll
-      for (int p4 = 0; p4 < KK / 4; ++p4) {
-        const float4 h = *reinterpret_cast<const float4*>(sHt + (NQ * e + c) * KK + 4 * p4);
-        hp[c][2 * p4] = f2{h.x, h.y};
-        hp[c][2 * p4 + 1] = f2{h.z, h.w};
-      }
-#pragma unroll
-    for (int m = 0; m < KK; ++m) hh[m] = sHHt[e * KK + m];
-#pragma unroll
-    for (int q = 0; q < KP; ++q) hh32[q] = f2{(float)hh[2 * q], (float)hh[2 * q + 1]};
-  };
-  load_basis();
-
-  f2 acc[NQ][KP], accB[KP];
-  auto zero_acc = [&]() {
-#pragma unroll
-    for (int c = 0; c < NQ; ++c)
-#pragma unroll
-      for (int p = 0; p < KP; ++p) acc[c][p] = f2{0.f, 0.f};
-#pragma unroll
-    for (int p = 0; p < KP; ++p) accB[p] = f2{0.f, 0.f};
-  };
-  zero_acc();
-
-  // the tile's 16-byte chunks of this lane: l + 64u (u < PFW - 1) and, for lanes < LASTL, the last
-  // (other lanes re-load chunk l: never staged; every lane issues the same loads), then the W tile
-  // when streamed (lanes < 16; others re-load chunk l)
-  auto prefetch = [&](u32x4 (&pf)[PFS], int64_t tile, int ti) {
-#ifdef CNMF_DIAG_L2
-    const unsigned char* xs = Xb + (size_t)(tile & 255) * XBW + 16 * l;
-#else
-    const unsigned char* xs = Xb + (size_t)tile * XBW + 16 * l;
-#endif
-#pragma unroll
-    for (int u = 0; u < PFW - 1; ++u) ld16(pf[u], xs + 1024 * u);
-    ld16(pf[PFW - 1], l < LASTL ? xs + 1024 * (PFW - 1) : xs);
-    if (!WRES) ld16(pf[PFW], (l < WBW / 16 && ti >= nres) ? Wb + (size_t)tile * WBW + 16 * l : xs);
-  };
-  auto stage = [&](const u32x4 (&pf)[PFS]) {
-    const unsigned addr = (unsigned)(uintptr_t)(stg + 16 * l);
-    stage_rec<0, PFW - 1>(addr, pf);
-    if (l < LASTL) st16<1024 * (PFW - 1)>(addr, pf[PFW - 1]);
-    if (!WRES && l < WBW / 16) st16<0>((unsigned)(uintptr_t)(wstg + 16 * l), pf[PFW]);
-  };
-
-  const int total = a.n_iter * nbt;
-  u32x4 pf[PD][PFS];
-  // W streamed: after each of the first PD sets one dummy store (to this workgroup's partial row,
-  // rewritten at the iteration's end), so that every set — the first PD too — has exactly PD stores
-  // younger than it when its step waits (set q < PD: PD - q dummies, then the W stores of bodies
-  // 0..q-1).  Counting PD stores that were never issued would let the set's last loads (the W tile)
-  // still be in flight when it is staged.
-  float* dummy = reinterpret_cast<float*>(a.partials + (size_t)b * RS) + 64 * w + l;
-#pragma unroll
-  for (int k = 0; k < PD; ++k) {
-    prefetch(pf[k], gw + (int64_t)NW * k, k);  // the host keeps nbt > PD
-#pragma unroll
-    for (int d = 0; d < NSTB; ++d) asm volatile("global_store_dword %0, %1, off" ::"v"(dummy), "v"(0) : "memory");
-  }
-  // W streamed: a tile's W store (body x) must have retired before its next load is issued (the
-  // prefetch at step x + nbt - PD); the step waits retire every operation older than the set they
-  // wait for, which covers that store when nbt >= 2·PD + 1 (the host guarantees it)
-  TL_START;
-
-  bool alive = true;
-  // position counters (wave-uniform, incremental: no division per tile): the tile being processed
-  // (iteration cur_it, index cur_i) and the next one to prefetch (nx_i).  Every step stages its
-  // register set and re-issues it unconditionally (past the launch's last position: the wave's
-  // first tile again, never used), so the count of younger loads is the same on every path.
-  int cur_i = 0, cur_it = 0, nx_i = PD;
-  auto step = [&](u32x4 (&pfk)[PFS]) {
-    // younger than this set's loads: the PD-1 later sets and the stores of the PD bodies since
-    // (for the launch's first PD sets the prologue's dummy stores): with W streamed its W store, and
-    // TOL the snapshot store every body issues (a loss iteration's W, else a dummy)
-    wait_set<PFS * (PD - 1) + NSTB * PD, PFS>(pfk);
-    stage(pfk);
-    prefetch(pfk, gw + (int64_t)NW * nx_i, nx_i);
-    if (++nx_i == nbt) nx_i = 0;
-  };
-  auto body = [&]() {
-    const int it = cur_it, i = cur_i;
-    if (++cur_i == nbt) {
-      cur_i = 0;
-      ++cur_it;
-    }
-    const bool last_it = it + 1 == a.n_iter;
-#ifdef CNMF_TOL_NOLOSS  // timing-only diagnostic: the TOL kernel without its loss iterations (never stops)
-    const bool loss_it = false;
-#else
-    const bool loss_it = TOL && ((it0 + it) % 10 == 0);  // check the state after it0 + it iterations
-#endif
-    const int64_t tile = gw + (int64_t)NW * i;
-    // phase 2 first where it does not need x: the sample's W row and den = w·HHᵀ[e] with its refined
-    // reciprocal (div_nr's v_rcp_f64 + Newton step, so w·num·r is div_nr's arithmetic) — their loads
-    // and their ~15-deep dependent chain then overlap phase 1 instead of following the reduce-scatter
-    // (round 5).  SK:553-629
-    const bool wr = WRES || i < nres;  // this tile's W resident
-    float* wt_ = wr ? wres + i * (TSW * KK) : reinterpret_cast<float*>(wstg);
-    float wv[KK];
-#pragma unroll
-    for (int m4 = 0; m4 < KK / 4; ++m4) {
-      const float4 v4 = *reinterpret_cast<const float4*>(wt_ + s * KK + 4 * m4);
-      wv[4 * m4] = v4.x;
-      wv[4 * m4 + 1] = v4.y;
-      wv[4 * m4 + 2] = v4.z;
-      wv[4 * m4 + 3] = v4.w;
-    }
-    const float wold32 = wt_[s * KK + e];
-    const double wold = (double)wold32;
-    double den = 0.0;
-    if constexpr (KK == 8) {
-      // den = w·HHᵀ[e] in packed fp32 (8 positive terms: no cancellation, ≤ 8 roundings), the
-      // update itself in fp64
-      f2 d2 = f2{0.f, 0.f};
-#pragma unroll
-      for (int q = 0; q < KP; ++q) d2 = __builtin_elementwise_fma(f2{wv[2 * q], wv[2 * q + 1]}, hh32[q], d2);
-      den = (double)(d2.x + d2.y);
-    } else {
-#pragma unroll
-      for (int m = 0; m < KK; ++m) den = fma((double)wv[m], hh[m], den);
-    }
-    if (a.l1W > 0.0) den += a.l1W;              // SK:616-617
-    if (a.l2W > 0.0) den = den + a.l2W * wold;  // SK:618-619
-    if (den == 0.0) den = EPS32;                // SK:620
-    double rden = __builtin_amdgcn_rcp(den);
-    rden = fma(rden, fma(-den, rden, 1.0), rden);
-    // phase 1: x along the lane's row, packed fp32 chains of 7 features folded into fp64
-    const float* xr = reinterpret_cast<const float*>(stg) + s * F + NQ * e;
-    float xv[NQ];
-#pragma unroll
-    for (int c = 0; c < NQ; ++c) xv[c] = xr[c];
-    double num;
-    if constexpr (KK == 8) {
-      // k = 8: ONE fp32 chain over the lane's 11 features, then the reduce-scatter over the
-      // sample's 8 lanes in fp32 (3 adds per value; a chain of 11 + 3 roundings, below the 7-term
-      // chains' error budget of §4), one DPP move per 32-bit value: level 1 pairs lane e with 7 - e
-      // (row_half_mirror: the other half of components), then e ^ 2 and e ^ 1 (quad_perm)
-      f2 ch[KP];
-#pragma unroll
-      for (int q = 0; q < KP; ++q) ch[q] = f2{0.f, 0.f};
-#pragma unroll
-      for (int c = 0; c < NQ; ++c) {
-        const f2 xx = f2{xv[c], xv[c]};
-#pragma unroll
-        for (int q = 0; q < KP; ++q) ch[q] = __builtin_elementwise_fma(xx, hp[c][q], ch[q]);
-      }
-      const bool b4 = (e & 4) != 0, b2 = (e & 2) != 0, b1 = (e & 1) != 0;
-      f2 r[2];
-#pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        const f2 keep = b4 ? ch[2 + m] : ch[m], send = b4 ? ch[m] : ch[2 + m];
-        r[m] = keep + f2{dppf<0x141>(send.x), dppf<0x141>(send.y)};  // row_half_mirror
-      }
-      const f2 keep2 = b2 ? r[1] : r[0], send2 = b2 ? r[0] : r[1];
-      const f2 t2 = keep2 + f2{dppf<0x4E>(send2.x), dppf<0x4E>(send2.y)};  // quad_perm [2,3,0,1]
-      const float keep1 = b1 ? t2.y : t2.x, send1 = b1 ? t2.x : t2.y;
-      num = (double)(keep1 + dppf<0xB1>(send1));  // quad_perm [1,0,3,2]
-    } else {
-      // k = 4: packed fp32 chains of 7 features folded into fp64, fp64 reduce-scatter over the
-      // sample's 4 lanes
-      double p[KK];
-#pragma unroll
-      for (int c0 = 0; c0 < NQ; c0 += 7) {
-        f2 ch[KP];
-#pragma unroll
-        for (int q = 0; q < KP; ++q) ch[q] = f2{0.f, 0.f};
-#pragma unroll
-        for (int c = c0; c < (c0 + 7 < NQ ? c0 + 7 : NQ); ++c) {
-          const f2 xx = f2{xv[c], xv[c]};
-#pragma unroll
-          for (int q = 0; q < KP; ++q) ch[q] = __builtin_elementwise_fma(xx, hp[c][q], ch[q]);
-        }
-#pragma unroll
-        for (int q = 0; q < KP; ++q) {
-          if (c0 == 0) {
-            p[2 * q] = (double)ch[q].x;
-            p[2 * q + 1] = (double)ch[q].y;
-          } else {
-            p[2 * q] += (double)ch[q].x;
-            p[2 * q + 1] += (double)ch[q].y;
-          }
-        }
-      }
-      const bool b1 = (e & 1) != 0, b2 = (e & 2) != 0;
-      double k2[2];
-#pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        const double keep = b2 ? p[2 + m] : p[m], send = b2 ? p[m] : p[2 + m];
-        k2[m] = keep + dpp64<0x4E>(send);  // quad_perm [2,3,0,1]
-      }
-      const double keep = b1 ? k2[1] : k2[0], send = b1 ? k2[0] : k2[1];
-      num = keep + dpp64<0xB1>(send);  // quad_perm [1,0,3,2]
-    }
-    if constexpr (TOL && WRES) {
-      // the W of the state a loss iteration checks, kept in LDS (written to HBM only on a stop)
-      if (loss_it) wsnapl[i * (TSW * KK) + s * KK + e] = wold32;
-    } else if constexpr (TOL) {
-      // W streamed: the W of the checked state, ONE store per body in every iteration (the steps'
-      // waits count it): a loss iteration stores the tile's W into the snapshot buffer, the others
-      // the same value over the wave's first tile there, which the next loss iteration overwrites
-      // (a stop happens only at the end of a loss iteration)
-      const int64_t tsel = loss_it ? tile : (int64_t)gw;
-      wsnap[(size_t)tsel * TSW * KK + l] = wold32;
-    }
-    if (loss_it) {
-      // ‖x − w·H‖² of the state before this update, the lane's NQ features (the last lane's overrun
-      // features past F belong to the next sample: masked)
-      float l2 = 0.f;
-#pragma unroll
-      for (int c = 0; c < NQ; ++c) {
-        f2 r2 = f2{0.f, 0.f};
-#pragma unroll
-        for (int q = 0; q < KP; ++q) r2 = __builtin_elementwise_fma(f2{wv[2 * q], wv[2 * q + 1]}, hp[c][q], r2);
-        const float r = NQ * e + c < F ? xv[c] - (r2.x + r2.y) : 0.f;
-        l2 = fmaf(r, r, l2);
-      }
-      lossacc += (double)l2;
-    }
-    const float wn = (float)(wold * (num * rden));  // SK:622-629 (div_nr's arithmetic)
-    wt_[s * KK + e] = wn;
-    if (!WRES) {  // lane l = (s, e); a resident tile's store goes to the dummy word
-      if (!wr) reinterpret_cast<float*>(Wb)[(size_t)tile * TSW * KK + l] = wn;
-      else asm volatile("global_store_dword %0, %1, off" ::"v"(dummy), "v"(0) : "memory");
-    }
-    // w'[s][·]: the sample's row back from LDS (this wave's writes above precede the reads)
-    f2 wp[KP];
-#pragma unroll
-    for (int m4 = 0; m4 < KK / 4; ++m4) {
-      const float4 v4 = *reinterpret_cast<const float4*>(wt_ + s * KK + 4 * m4);
-      wp[2 * m4] = f2{v4.x, v4.y};
-      wp[2 * m4 + 1] = f2{v4.z, v4.w};
-    }
-    // phase 3: A[·][f] += w'·x[f], B[e][·] += w'_e·w' (fp32 per lane over the iteration)
-#pragma unroll
-    for (int c = 0; c < NQ; ++c) {
-      const f2 xx = f2{xv[c], xv[c]};
-#pragma unroll
-      for (int q = 0; q < KP; ++q) acc[c][q] = __builtin_elementwise_fma(xx, wp[q], acc[c][q]);
-    }
-#pragma unroll
-    for (int q = 0; q < KP; ++q) accB[q] = __builtin_elementwise_fma(f2{wn, wn}, wp[q], accB[q]);
-    if (i + 1 != nbt) return;
-
-    // ---- end of this wave's iteration: its sums over the sample lanes of each e -> LDS
-    // (reduce-scatter, round 6: value j = c·KK + 2q + comp (A), NQ·KK + 2q + comp (B); row r of the
-    // wave ends with the quarter of the values scatter_over_samples names, written by the row's
-    // lanes of sample 0, in pairs of floats)
-    {
-      float vv[NACC];
-#pragma unroll
-      for (int c = 0; c < NQ; ++c)
-#pragma unroll
-        for (int q = 0; q < KP; ++q) {
-          vv[c * KK + 2 * q] = acc[c][q].x;
-          vv[c * KK + 2 * q + 1] = acc[c][q].y;
-        }
-#pragma unroll
-      for (int q = 0; q < KP; ++q) {
-        vv[NQ * KK + 2 * q] = accB[q].x;
-        vv[NQ * KK + 2 * q + 1] = accB[q].y;
-      }
-      scatter_over_samples<NL>(vv);
-      constexpr int NQT = NACC / 4;
-      static_assert(NQT % 2 == 0, "the quarters are written in pairs of floats");
-      const int r = l >> 4;
-      float* rw = red + (w * NL + e) * NACC + (NACC / 2) * (r >> 1) + NQT * (r & 1);
-      if ((l & 15) < NL)
-#pragma unroll
-        for (int j = 0; j < NQT; j += 2) *reinterpret_cast<float2*>(rw + j) = make_float2(vv[j], vv[j + 1]);
-    }
-    zero_acc();
-    if (TOL) {  // the wave's loss sum (zero outside loss iterations), fixed xor tree
-      const double v = wave_sum(lossacc);
-      if (l == 0) sLoss[w] = v;
-      lossacc = 0.0;
-    }
-    __syncthreads();
-    TL_PRE(it);
-    // the workgroup's fp64 row [K][V] (+ the loss): the four waves' sums in wave order (deterministic)
-    {
-      double* prow = a.partials + (size_t)b * RS;
-      const bool plain = sFlag[4] != 0;  // the group's rows through the XCD's L2 (l2rows)
-      auto row_val = [&](int o) {
-        const int j = o / V;
-        const int v = o - j * V;
-        const int ee = v < F ? v / NQ : j;
-        const int idx = v < F ? (v - NQ * ee) * KK + j : NQ * KK + (v - F);
-        const float* rr = red + ee * NACC + idx;
-        constexpr int WS = NL * NACC;  // wave stride
-        return ((double)rr[0] + (double)rr[WS]) + ((double)rr[2 * WS] + (double)rr[3 * WS]);
-      };
-      // pairs of doubles, one 16-byte store each (round 6); TOL: the loss at NOUT, a zero pad after it
-      auto val = [&](int o) {
-        if (o < NOUT) return row_val(o);
-        return (TOL && o == NOUT) ? (sLoss[0] + sLoss[1]) + (sLoss[2] + sLoss[3]) : 0.0;
-      };
-      if constexpr (R6) {
-        for (int c = t; c < RS / 2; c += NT) {
-          const double v0 = val(2 * c), v1 = val(2 * c + 1);
-          if (plain) st16_plain(prow + 2 * c, v0, v1);
-          else st16_sc1v(prow + 2 * c, v0, v1);
-        }
-      } else {
-        for (int o = t; o < NOUTT; o += NT) __hip_atomic_store(prow + o, val(o), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave: its sc1 stores landed
-    __syncthreads();
-    TL(it, 0);
-    if (t == 0) {
-      const uint32_t old = __hip_atomic_fetch_add(cnt_group, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      sFlag[0] = old == (uint32_t)((it + 1) * gs - 1);
-      sFlag[1] = 0;
-      sFlag[2] = 1;
-      sFlag[3] = 0;
-    }
-    __syncthreads();
-    // the last iteration of the launch waits for the flag too when it checks the tolerance (a stop
-    // there must reach every workgroup before it writes W back)
-    const bool must_wait = !last_it || loss_it;
-    if (sFlag[0]) {  // group combiner
-      TL_LV(it, g, 0);
-      if constexpr (R6) sum_rows_v<RS>(a.partials, g, NG, gs, nullptr, a.groups + (size_t)g * RS, t);
-      else sum_rows_n<RS>(a.partials, g, NG, gs, nullptr, a.groups + (size_t)g * RS, t);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      TL_LV(it, g, 1);
-      if (t == 0) {
-        const uint32_t old = __hip_atomic_fetch_add(cnt_top, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        sFlag[1] = old == (uint32_t)((it + 1) * NG - 1);
-      }
-      __syncthreads();
-      if (sFlag[1]) {  // top combiner: AB
-        TL_LV(it, TL_LVG, 0);
-        if constexpr (R6) {
-          sum_rows_v<RS>(a.groups, 0, 1, NG, sAB, a.AB, t);
-          if (MULTI) __syncthreads();  // the exchange reads sAB in sum_rows_n's thread mapping
-        } else {
-          sum_rows_n<RS>(a.groups, 0, 1, NG, sAB, a.AB, t);
-        }
-        if (MULTI) xchg_allreduce_n<NOUTT>(a.xctl, a.AB, sAB, err, it, t);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        TL_LV(it, TL_LVG, 1);
-        // (after the barrier: the summed loss sAB[NOUT] was written by another thread)
-        if (TOL && loss_it && t == 0) {  // SK:872-884 on the state after it0 + it iterations
-          const int gi = it0 + it;
-          const double errv = sqrt(fmax(sAB[NOUT], 0.0));
-          const int slot = gi / 10;
-          if (slot < (int)ld_sc1(a.tolctl + TC_CAP)) st_sc1(a.tolctl + TC_ERRS + slot, errv);
-          st_sc1(a.tolctl + TC_NERR, (double)(slot + 1));
-          if (gi == 0) {
-            sLoss[4] = sLoss[5] = errv;
-            st_sc1(a.tolctl + TC_INIT, errv);
-            st_sc1(a.tolctl + TC_PREV, errv);
-          } else if ((sLoss[5] - errv) / sLoss[4] < tolv) {
-            sFlag[3] = 1;
-          } else {
-            sLoss[5] = errv;
-            st_sc1(a.tolctl + TC_PREV, errv);
-          }
-        }
-        if (TOL && loss_it) __syncthreads();  // sFlag[3] (the decision) for the whole workgroup
-        if (t == 0 && must_wait)
-          __hip_atomic_store(flag, (uint32_t)(it + 1) | (sFlag[3] ? FLAG_STOP : 0u), __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-        TL_PUB(it);
-      }
-    }
-    const bool top = sFlag[1] != 0;
-    if (!top && must_wait) {
-      if (t == 0) {
-        const uint32_t want = (uint32_t)(it + 1);
-        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-        uint32_t f;
-        while (true) {  // the flag and the error word in one batch: one round trip per round
-          const uint32_t ev = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          f = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if ((f & ~FLAG_STOP) >= want) break;
-          if (ev != 0u) {
-            sFlag[2] = 0;
-            break;
-          }
-          if (__builtin_amdgcn_s_memrealtime() - t0 > sl::SPIN_TIMEOUT) {
-            __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            sFlag[2] = 0;
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-        }
-        if (TOL && (f & FLAG_STOP)) sFlag[3] = 1;
-        TL_SEEN(it);
-      }
-      __syncthreads();
-      if (!sFlag[2]) {  // a workgroup never arrived (not co-resident): give up, error word set
-        alive = false;
-        return;
-      }
-    }
-    if (TOL && sFlag[3]) {
-      // stopped by the tolerance test: the state after it0 + it iterations (W: the loss
-      // iteration's LDS snapshot written back here, or the host copies the streamed-W snapshot
-      // buffer; H = sH not updated); the host clears the flag word after the launch
-      alive = false;
-      if (WRES)
-        for (int c = l; c < nbt * (WBW / 16); c += 64) {
-          const int ii = c / (WBW / 16), ch = c - ii * (WBW / 16);
-          *reinterpret_cast<u32x4*>(Wb + (size_t)(gw + (int64_t)NW * ii) * WBW + 16 * ch) =
-              *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(wsnapl) + ii * WBW + 16 * ch);
-        }
-      if (!top) return;
-      for (int o = t; o < KK * F; o += NT) a.H64[o] = sH[o];
-      for (int o = t; o < F * KK; o += NT) {
-        const int f = o / KK;
-        const int j = o - f * KK;
-        a.Ht[o] = sH[j * F + f];
-      }
-      if (t < KK * KK) a.HHt[t] = reinterpret_cast<const double*>(smem + G_::L_HHT)[t];
-      if (t < NG) __hip_atomic_store(a.cnt + CNT_GROUP0 + 32 * t, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (l2rows)
-        for (int o = t; o < G; o += NT) __hip_atomic_store(a.cnt + CNT_XCC0 + o, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (t == 0) {
-        __hip_atomic_store(cnt_top, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        st_sc1(a.tolctl + TC_DONE, (double)(it0 + it));
-        st_sc1(a.tolctl + TC_STOPPED, 1.0);
-        st_sc1(a.tolctl + TC_IN_SNAP, WRES ? 0.0 : 1.0);
-        if (MULTI)
-          __hip_atomic_fetch_add(a.xctl + XC_GEN, (uint64_t)(it + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      return;
-    }
-    if (last_it) {
-      alive = false;
-      if (WRES || nres > 0)  // this wave's resident W back to HBM, once per launch
-        for (int c = l; c < (WRES ? nbt : min(nres, nbt)) * (WBW / 16); c += 64) {
-          const int ii = c / (WBW / 16), ch = c - ii * (WBW / 16);
-          *reinterpret_cast<u32x4*>(Wb + (size_t)(gw + (int64_t)NW * ii) * WBW + 16 * ch) =
-              *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(wres) + ii * WBW + 16 * ch);
-        }
-      if (!top) return;
-      // the last combiner of the launch: every other workgroup has arrived for the last time
-      if (a.apply_last) {
-        if constexpr (R6) wt_update_basis<KK>(smem, t, a.l1H, a.l2H);
-        else wt_update_basis_r5<KK>(smem, t, a.l1H, a.l2H);
-      }
-      for (int o = t; o < KK * F; o += NT) a.H64[o] = sH[o];
-      for (int o = t; o < F * KK; o += NT) {
-        const int f = o / KK;
-        const int j = o - f * KK;
-        a.Ht[o] = sH[j * F + f];
-      }
-      if (t < KK * KK) a.HHt[t] = reinterpret_cast<const double*>(smem + G_::L_HHT)[t];
-      if (t < NG) __hip_atomic_store(a.cnt + CNT_GROUP0 + 32 * t, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (l2rows)
-        for (int o = t; o < G; o += NT) __hip_atomic_store(a.cnt + CNT_XCC0 + o, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (t == 0) {
-        __hip_atomic_store(cnt_top, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (!must_wait)  // (else workgroups may still poll it: the host clears it after the launch)
-          __hip_atomic_store(flag, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (TOL) {
-          st_sc1(a.tolctl + TC_DONE, (double)(it0 + a.n_iter));
-          st_sc1(a.tolctl + TC_STOPPED, 0.0);
-        }
-        if (MULTI)  // the next launch's generations follow this one's
-          __hip_atomic_fetch_add(a.xctl + XC_GEN, (uint64_t)a.n_iter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      return;
-    }
-    if (!top) {
-      if constexpr (!R6) {
-        for (int o = t; o < NOUTT; o += NT) sAB[o] = ld_sc1(a.AB + o);
-      } else {  // 16-byte sc1 loads, all in flight together (round 6)
-        constexpr int NCH = RS / 2;
-        const int c0 = t < NCH ? t : 0, c1 = t + NT < NCH ? t + NT : 0;
-        u32x4 r0, r1;
-        ld16_sc1(r0, a.AB + 2 * c0);
-        if (NCH > NT) ld16_sc1(r1, a.AB + 2 * c1);
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(r0), "+v"(r1) : : "memory");
-        if (t < NCH) {
-          sAB[2 * t] = lo_d(r0);
-          sAB[2 * t + 1] = hi_d(r0);
-        }
-        if (t + NT < NCH) {
-          sAB[2 * (t + NT)] = lo_d(r1);
-          sAB[2 * (t + NT) + 1] = hi_d(r1);
-        }
-      }
-      __syncthreads();
-      TL_AB(it);
-      if (TOL && loss_it && t == 0) {  // the top went on: prev <- this check's error
-        const double errv = sqrt(fmax(sAB[NOUT], 0.0));
-        if (it0 + it == 0) sLoss[4] = errv;
-        sLoss[5] = errv;
-      }
-    }
-    if (l2rows && it == 0 && w == 0) {
-      // every member has written its XCC (at its start, before its first arrival): the group's rows
-      // may go through the L2 when all of them share this workgroup's XCC (the same answer in every
-      // member: they read the same table)
-      const uint32_t xm = l < gs ? __hip_atomic_load(a.cnt + CNT_XCC0 + g + NG * l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                 : (uint32_t)sFlag[5];
-      const bool same = __ballot(xm != (uint32_t)sFlag[5]) == 0;
-      if (l == 0) sFlag[4] = same ? 1 : 0;
-    }
-    if constexpr (R6) wt_update_basis<KK>(smem, t, a.l1H, a.l2H);
-    else wt_update_basis_r5<KK>(smem, t, a.l1H, a.l2H);
-    TL_UPD(it);
-    load_basis();
-    TL(it, 1);
-  };
-
-  for (int p = 0; p < total && alive; p += PD) {
-#pragma unroll
-    for (int k = 0; k < PD; ++k) {
-      step(pf[k]);
-      if (p + k < total && alive) body();
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no load outlives the workgroup
-}
-
-// ------------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------------
 // mu_iter_mf8_kernel<WRES, PD, MULTI, TOL> — k = 8 (cfg3) wave tiles on the matrix cores.
 //
@@ -4710,35 +3229,6 @@ __global__ __launch_bounds__(NT, 1) void mu_iter_wt_kernel(PersistArgs a) {
 // in-launch exchange (MULTI) and the device tolerance test (TOL: ‖x − w·H‖² via 12 more MFMAs
 // R = W·H in the loss iterations) are mu_iter_wt_kernel's.
 // ------------------------------------------------------------------------------------------------
-namespace wt {
-typedef float f4v __attribute__((ext_vector_type(4)));
-struct GeoMF8 {
-  static constexpr int K = 8, TSW = 16, V = F + 8, NOUT = 8 * V;
-  static constexpr int NL = 8, NQ = 11;  // the sHt image wt_derive_basis<8> writes (Geo<8>'s)
-  static constexpr int XBW = TSW * F * 4;                  // 5184 B of X per tile
-  static constexpr int NCHW = XBW / 16;                    // 324 chunks
-  static constexpr int PFW = (NCHW + 63) / 64;             // 6 loads per lane
-  static constexpr int LASTL = NCHW - 64 * (PFW - 1);      // 4
-  static constexpr int PADB = 16;                          // phase 1 reads 3 floats past the tile
-  static constexpr int XSTR = XBW + PADB;
-  static constexpr int WBW = TSW * 8 * 4;                  // 512 B of W per tile
-  static constexpr int KS1 = 21, NCH1 = 7, NB3 = 6;
-  static constexpr int L_STG = 0;                                       // [NWV][XSTR]
-  static constexpr int L_WSTG = L_STG + NWV * XSTR;                     // streamed W: [NWV][WBW]
-  static constexpr int L_WP = (L_WSTG + NWV * WBW + 15) / 16 * 16;      // W' operand [NWV][16][16] fp32
-  static constexpr int L_RED = L_WP + NWV * 16 * 16 * 4;                // [NWV][8][V] fp64
-  static constexpr int L_H = L_RED + NWV * 8 * V * 8;                   // H fp64 [8][F]
-  static constexpr int L_AB = L_H + 8 * F * 8;                          // AB fp64 (+ the loss)
-  static constexpr int L_HT = L_AB + (NOUT + 2) * 8;                    // (wt_derive_basis' Hᵀ image)
-  static constexpr int L_HHT = L_HT + NL * NQ * 8 * 4;                  // HHᵀ fp64 [8][8]
-  static constexpr int L_FLAG = L_HHT + 8 * 8 * 8;                      // 8 ints
-  static constexpr int L_LOSS = L_FLAG + 32;                            // [NWV] wave loss sums, init, prev
-  static constexpr int L_WRES = (L_LOSS + 8 * 8 + 15) / 16 * 16;        // [NWV][nbt_max][WBW]
-  static_assert(NCHW * 16 == XBW && L_HT % 16 == 0 && L_RED % 16 == 0, "layout");
-  static_assert(NOUT * 8 >= NWV * 64 * 4, "the prologue's dummy stores stay inside the partial row");
-};
-__device__ __forceinline__ f4v mfma4(float a, float b, f4v c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-}  // namespace wt
 
 template <bool WRES, int PD, bool MULTI = false, bool TOL = false>
 __global__ __launch_bounds__(NT, 1) void mu_iter_mf8_kernel(PersistArgs a) {
@@ -6134,7 +4624,6 @@ __global__ __launch_bounds__(256) void hbm_probe_kernel(const u32x4* __restrict_
 // ------------------------------------------------------------------------------------------------
 // host side: kernel selection, occupancy-derived grid, launches
 // ------------------------------------------------------------------------------------------------
-using PassFn = const void*;
 
 struct PassKernel {
   PassFn fn;
@@ -6210,7 +4699,6 @@ static bool pick_mfma(int x_dtype, int F, int k, PassKernel* out) {
 
 static int padded_k(int k) { return k <= 4 ? 4 : (k <= 8 ? 8 : 16); }
 
-static constexpr size_t kMaxLds = 160 * 1024;
 // A/B switches for benchmarking: CNMF_PASS_KERNEL=valu|mfma|sl restricts the accumulating pass to
 // one kernel family (CNMF_FORCE_VALU=1 is the older spelling of "valu")
 static const char* pass_choice() {
@@ -6290,7 +4778,7 @@ static std::mutex g_occ_mu;
 static std::unordered_map<OccKey, int64_t, OccHash> g_occ;
 
 // max co-resident workgroups of this kernel on the current device (occupancy × CUs), cached
-static int64_t max_resident(PassFn fn, size_t lds) {
+int64_t max_resident(PassFn fn, size_t lds) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return -1;
   OccKey key{dev, fn, lds};
@@ -6356,188 +4844,32 @@ static size_t reduce_lds(int n_out, int fuse, int F, int k) {
   return d * sizeof(double);
 }
 
-// ------------------------------------------------------------------------------------------------
-// GPU NNDSVD initialisation (sklearn's _initialize_nmf SK:317-373 over
-// randomized_svd, extmath.py:530-604).  sklearn's range finder alternates Q <- lu(X·Q),
-// Q <- lu(Xᵀ·Q): only span(Q) matters to the result (U, s, Vt are invariant under an orthonormal
-// change of basis of the range; svd_flip fixes the signs), and span(Xᵀ·X·Q) needs only the F × F
-// Gram matrix C = XᵀX.  So the device does the work that scales with N:
-//   ig_gram_kernel    C = XᵀX and the column sums of X (fp64, per-workgroup partial rows, reduced by
-//                     cnmf_reduce_partials) — one pass over X;
-//   ig_xm_kernel      U = X·M (M = F × k from the small host algebra), fp64 — one pass over X;
-//   ig_stats_kernel   per column of U: Σ max(u,0)², Σ min(u,0)², and the first entry of largest |u|
-//                     (svd_flip's u-based sign) — per-workgroup rows;
-//   ig_fill_kernel    W from U: sqrt(S0)|u| (j = 0) or lbd·part(sign·u)/‖part‖, < eps -> 0, and the
-//                     nndsvda fill — in X's dtype;
-// while the host does sklearn's F × r / r × r algebra in fp64 (cnmf_amd/gpu_init.py).
-// ------------------------------------------------------------------------------------------------
-namespace ig {
-constexpr int FP = 96;   // features padded (F <= 96)
-constexpr int GT = 64;   // rows per staged tile
-constexpr int KMAX = 16;
-}  // namespace ig
-
-// C = XᵀX (F × F) and colsum (F) of this workgroup's rows [r0, r1): thread (a, c) owns C rows
-// 3a..3a+2 × columns 12c..12c+11 (fp64 registers); the tile is staged in LDS as fp64 [GT][FP].
-// Output row: [F·F | F].
-template <typename TX>
-__global__ __launch_bounds__(256) void ig_gram_kernel(const TX* __restrict__ X, int64_t n_rows, int F,
-                                                      int64_t rows_per_block, double* __restrict__ partials) {
-  using namespace ig;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  double* tile = reinterpret_cast<double*>(smem);  // [GT][FP]
-  const int t = threadIdx.x;
-  const int a = t >> 3, c = t & 7;
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  const int64_t r1 = r0 + rows_per_block < n_rows ? r0 + rows_per_block : n_rows;
-  double acc[3][12], cs[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    cs[i] = 0.0;
-#pragma unroll
-    for (int j = 0; j < 12; ++j) acc[i][j] = 0.0;
-  }
-  for (int64_t rt = r0; rt < r1; rt += GT) {
-    const int nr = (int)(r1 - rt < GT ? r1 - rt : GT);
-    __syncthreads();
-    for (int e = t; e < GT * FP; e += 256) {
-      const int r = e / FP, f = e - r * FP;
-      tile[e] = (r < nr && f < F) ? (double)to_c(*(X + (rt + r) * F + f)) : 0.0;
-    }
-    __syncthreads();
-    for (int r = 0; r < nr; ++r) {
-      const double* row = tile + r * FP;
-      double xa[3], xb[12];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) xa[i] = row[3 * a + i];
-#pragma unroll
-      for (int j = 0; j < 12; ++j) xb[j] = row[12 * c + j];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 12; ++j) acc[i][j] = fma(xa[i], xb[j], acc[i][j]);
-        cs[i] += xa[i];
-      }
-    }
-  }
-  double* prow = partials + (size_t)blockIdx.x * (F * F + F);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const int fi = 3 * a + i;
-    if (fi >= F) continue;
-#pragma unroll
-    for (int j = 0; j < 12; ++j) {
-      const int fj = 12 * c + j;
-      if (fj < F) prow[fi * F + fj] = acc[i][j];
-    }
-    if (c == 0) prow[F * F + fi] = cs[i];
-  }
+int device_cus() {
+  static int cus[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus[dev] = 0;
+  return cus[dev];
 }
 
-// U[n][j] = Σ_f X[n][f]·M[f][j] (fp64), k <= 16: thread = (row of the tile, component group)
-template <typename TX>
-__global__ __launch_bounds__(256) void ig_xm_kernel(const TX* __restrict__ X, int64_t n_rows, int F, int k,
-                                                    const double* __restrict__ M, double* __restrict__ U) {
-  using namespace ig;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  double* sM = reinterpret_cast<double*>(smem);  // [F][k]
-  float* tile = reinterpret_cast<float*>(smem + (size_t)FP * KMAX * 8);  // [GT][F + 1] (fp32 copy; exact for f32/bf16)
-  double* tile64 = reinterpret_cast<double*>(smem + (size_t)FP * KMAX * 8);  // f64 X: [GT][F + 1]
-  const int t = threadIdx.x;
-  for (int e = t; e < F * k; e += 256) sM[e] = M[e];
-  const int r = t & (GT - 1), jg = t >> 6;  // 4 component groups: j = jg, jg + 4, ...
-  const int64_t n_tiles = (n_rows + GT - 1) / GT;
-  for (int64_t tb = blockIdx.x; tb < n_tiles; tb += gridDim.x) {
-    const int64_t row0 = tb * GT;
-    const int nr = (int)(n_rows - row0 < GT ? n_rows - row0 : GT);
-    __syncthreads();
-    for (int e = t; e < nr * F; e += 256) {
-      const int rr = e / F, f = e - rr * F;
-      if (std::is_same<TX, double>::value)
-        tile64[rr * (F + 1) + f] = (double)to_c(*(X + row0 * F + e));
-      else
-        tile[rr * (F + 1) + f] = (float)to_c(*(X + row0 * F + e));
-    }
-    __syncthreads();
-    if (r < nr) {
-      for (int j = jg; j < k; j += 4) {
-        double u = 0.0;
-        for (int f = 0; f < F; ++f) {
-          const double x = std::is_same<TX, double>::value ? tile64[r * (F + 1) + f] : (double)tile[r * (F + 1) + f];
-          u = fma(x, sM[f * k + j], u);
-        }
-        U[(row0 + r) * k + j] = u;
-      }
-    }
-  }
-}
-
-// per column j of U (N × k fp64) over this workgroup's rows: [Σ max(u,0)², Σ min(u,0)², max|u|,
-// the u at the first row attaining it, that row] — 5 doubles per column
-__global__ __launch_bounds__(256) void ig_stats_kernel(const double* __restrict__ U, int64_t n_rows, int k,
-                                                       int64_t rows_per_block, double* __restrict__ out) {
-  __shared__ double red[256][5];
-  const int t = threadIdx.x;
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  const int64_t r1 = r0 + rows_per_block < n_rows ? r0 + rows_per_block : n_rows;
-  for (int j = 0; j < k; ++j) {
-    double sp = 0.0, sn = 0.0, mx = -1.0, mv = 0.0, mi = 0.0;
-    for (int64_t r = r0 + t; r < r1; r += 256) {  // rows ascending per thread: first max kept
-      const double u = U[r * k + j];
-      if (u > 0.0) sp = fma(u, u, sp);
-      if (u < 0.0) sn = fma(u, u, sn);
-      if (fabs(u) > mx) {
-        mx = fabs(u);
-        mv = u;
-        mi = (double)r;
-      }
-    }
-    red[t][0] = sp;
-    red[t][1] = sn;
-    red[t][2] = mx;
-    red[t][3] = mv;
-    red[t][4] = mi;
-    __syncthreads();
-    if (t == 0) {  // fixed order; ties on |u|: the lowest row (np.argmax's first occurrence)
-      double a0 = 0.0, a1 = 0.0, bm = -1.0, bv = 0.0, bi = 0.0;
-      for (int i = 0; i < 256; ++i) {
-        a0 += red[i][0];
-        a1 += red[i][1];
-        if (red[i][2] > bm || (red[i][2] == bm && red[i][4] < bi)) {
-          bm = red[i][2];
-          bv = red[i][3];
-          bi = red[i][4];
-        }
-      }
-      double* o = out + ((size_t)blockIdx.x * k + j) * 5;
-      o[0] = a0;
-      o[1] = a1;
-      o[2] = bm;
-      o[3] = bv;
-      o[4] = bi;
-    }
-    __syncthreads();
-  }
-}
-
-// W[n][j] from U[n][j]: v = coef_j · part_j(sign_j · u) with part 0 = |u|, 1 = max(u,0), 2 = |min(u,0)|;
-// v < eps -> 0; then v == 0 -> fill (nndsvda: X.mean(); nndsvd / nndsvdar: 0)
-template <typename TW>
-__global__ __launch_bounds__(256) void ig_fill_kernel(const double* __restrict__ U, int64_t n, int k,
-                                                      const double* __restrict__ coef, const int* __restrict__ part,
-                                                      const double* __restrict__ sgn, double eps, double fill,
-                                                      TW* __restrict__ W) {
-  const int64_t total = n * k;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int j = (int)(e % k);
-    const double u = sgn[j] * U[e];
-    const int pj = part[j];
-    const double p = pj == 0 ? fabs(u) : (pj == 1 ? (u > 0.0 ? u : 0.0) : (u < 0.0 ? -u : 0.0));
-    double v = pj == 0 ? coef[j] * p : p * coef[j];
-    if (v < eps) v = 0.0;
-    if (v == 0.0) v = fill;
-    W[e] = (TW)v;
-  }
+// the k = 8 matrix-core wave tiles (layout 5): slower than the VALU wave tiles on every box measured
+// (DESIGN §3.0), so since round 6 they exist in the diagnostic build only (VERDICT r5 item 8); the
+// product refuses layout 5 with CNMF_ERR_ARG
+PassFn mf8_fn(bool wres, bool multi, bool tol) {
+#ifndef CNMF_DIAG
+  (void)wres; (void)multi; (void)tol;
+  return nullptr;
+#else
+  if (wres)
+    return tol ? (multi ? reinterpret_cast<PassFn>(&mu_iter_mf8_kernel<true, 3, true, true>)
+                        : reinterpret_cast<PassFn>(&mu_iter_mf8_kernel<true, 3, false, true>))
+               : (multi ? reinterpret_cast<PassFn>(&mu_iter_mf8_kernel<true, 3, true, false>)
+                        : reinterpret_cast<PassFn>(&mu_iter_mf8_kernel<true, 3, false, false>));
+  return tol ? (multi ? reinterpret_cast<PassFn>(&mu_iter_mf8_kernel<false, 3, true, true>)
+                      : reinterpret_cast<PassFn>(&mu_iter_mf8_kernel<false, 3, false, true>))
+             : (multi ? reinterpret_cast<PassFn>(&mu_iter_mf8_kernel<false, 3, true, false>)
+                      : reinterpret_cast<PassFn>(&mu_iter_mf8_kernel<false, 3, false, false>));
+#endif
 }
 
 }  // namespace cnmf
@@ -8185,6 +6517,20 @@ int64_t cnmf_pass_blocks(int64_t n_rows, int n_features, int k, int x_dtype) {
   return nb;
 }
 
+// the ragged tail (< 64 rows past n_full tiles) on one workgroup of a 64-sample pass, partial row g
+static int launch_tail(const PassKernel& pk, size_t lds, const void* X, void* W, const double* Ht,
+                       const double* HHt, double* partials, int64_t n_rows, int64_t n_full, int64_t g, int F, int k,
+                       double l1_W, double l2_W, int flags, hipStream_t s) {
+  if (max_resident(pk.fn, lds) <= 0) return set_err(CNMF_ERR_HIP, "occupancy query failed");
+  const void* Xt = static_cast<const unsigned char*>(X) + n_full * TS * F * (int64_t)pk.sx;
+  void* Wt = static_cast<float*>(W) + n_full * TS * k;
+  double* pt = partials ? partials + g * (int64_t)k * (F + k) : nullptr;
+  int64_t rows = n_rows - n_full * TS, one = 1;
+  void* args[] = {(void*)&Xt, &Wt, (void*)&Ht, (void*)&HHt, &pt, &rows, &F, &k, &l1_W, &l2_W, &flags, (void*)&one};
+  HIP_CHECK(hipLaunchKernel(pk.fn, dim3(1), dim3(NT), args, lds, s));
+  return CNMF_OK;
+}
+
 int cnmf_mu_sample_pass(const void* X, int x_dtype, void* W, const double* Ht, const double* HHt,
                         double* partials, int64_t n_rows, int n_features, int k, double l1_W,
                         double l2_W, int flags, void* stream) {
@@ -8196,8 +6542,7 @@ int cnmf_mu_sample_pass(const void* X, int x_dtype, void* W, const double* Ht, c
     return set_err(CNMF_ERR_ARG, "invalid flags %d", flags);
   if ((flags & (CNMF_PASS_ACCUMULATE | CNMF_PASS_LOSS)) && !partials)
     return set_err(CNMF_ERR_ARG, "partials required");
-  if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(W) & 15))
-    return set_err(CNMF_ERR_ALIGN, "X and W must be 16-byte aligned");
+  if (int st = check_xw_aligned(X, W)) return st;
   // every launch of a shape uses the grid of its main (accumulating) kernel, so the number of
   // partial rows is one per shape (cnmf_pass_blocks) whatever the flags
   PassKernel pmain;
@@ -8221,19 +6566,11 @@ int cnmf_mu_sample_pass(const void* X, int x_dtype, void* W, const double* Ht, c
       HIP_CHECK(hipGetLastError());
     }
     if (!tail) return CNMF_OK;
-    // the ragged tail (< 64 rows) on one workgroup of the VALU pass, partial row g
-    PassKernel pk;
+    PassKernel pk;  // the VALU pass
     size_t lds = 0;
     st = select_pass(x_dtype, n_features, k, &pk, &lds, false);
     if (st) return st;
-    if (max_resident(pk.fn, lds) <= 0) return set_err(CNMF_ERR_HIP, "occupancy query failed");
-    const void* Xt = static_cast<const float*>(X) + n_full * TS * F;
-    void* Wt = static_cast<float*>(W) + n_full * TS * k;
-    double* pt = partials + g * (int64_t)k * (F + k);
-    int64_t rows = n_rows - n_full * TS, one = 1;
-    void* args[] = {(void*)&Xt, &Wt, (void*)&Ht, (void*)&HHt, &pt, &rows, &F, &k, &l1_W, &l2_W, &flags, (void*)&one};
-    HIP_CHECK(hipLaunchKernel(pk.fn, dim3(1), dim3(NT), args, lds, s));
-    return CNMF_OK;
+    return launch_tail(pk, lds, X, W, Ht, HHt, partials, n_rows, n_full, g, F, k, l1_W, l2_W, flags, s);
   }
   if (use_bfw(x_dtype, n_features, k) && (flags & CNMF_PASS_UPDATE_W) && partials) {
     const int64_t n_full = n_rows / TS;
@@ -8247,15 +6584,8 @@ int cnmf_mu_sample_pass(const void* X, int x_dtype, void* W, const double* Ht, c
       HIP_CHECK(hipLaunchKernel(bfw_fn(F, k), dim3((unsigned)g), dim3(NT), args, lb, s));
     }
     if (n_rows % TS == 0) return CNMF_OK;
-    // the ragged tail (< 64 rows) on one workgroup of the 64-sample matrix-core pass, partial row g
-    if (max_resident(pmain.fn, lmain) <= 0) return set_err(CNMF_ERR_HIP, "occupancy query failed");
-    const void* Xt = static_cast<const bf16_t*>(X) + n_full * TS * F;
-    void* Wt = static_cast<float*>(W) + n_full * TS * k;
-    double* pt = partials ? partials + g * (int64_t)k * (F + k) : nullptr;
-    int64_t rows = n_rows - n_full * TS, one = 1;
-    void* args[] = {(void*)&Xt, &Wt, (void*)&Ht, (void*)&HHt, &pt, &rows, &F, &k, &l1_W, &l2_W, &flags, (void*)&one};
-    HIP_CHECK(hipLaunchKernel(pmain.fn, dim3(1), dim3(NT), args, lmain, s));
-    return CNMF_OK;
+    // the 64-sample matrix-core pass
+    return launch_tail(pmain, lmain, X, W, Ht, HHt, partials, n_rows, n_full, g, F, k, l1_W, l2_W, flags, s);
   }
   PassKernel pk = pmain;
   size_t lds = lmain;
@@ -8405,8 +6735,7 @@ int cnmf_als_sample_pass(const void* X, int x_dtype, void* W, const double* Ht, 
   if (!X || !W || !Ht || !table || (accumulate && !partials)) return set_err(CNMF_ERR_ARG, "null pointer argument");
   if (k > ALS_MAX_K) return set_err(CNMF_ERR_UNSUPPORTED, "constrained ALS supports k <= %d (got %d)", ALS_MAX_K, k);
   if (!(sum_to_one >= 0.0)) return set_err(CNMF_ERR_ARG, "sum_to_one must be >= 0");
-  if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(W) & 15))
-    return set_err(CNMF_ERR_ALIGN, "X and W must be 16-byte aligned");
+  if (int st = check_xw_aligned(X, W)) return st;
   PassKernel pmain;
   size_t lmain = 0;
   int st = select_pass(x_dtype, n_features, k, &pmain, &lmain);
@@ -8707,121 +7036,6 @@ static int64_t persist_teams_grid(int64_t n_tiles, bool multi, int layout, size_
   return G;
 }
 
-// ---- variant 4: barrier-free wave tiles (mu_iter_wt_kernel<K, WRES, PD, MULTI>: one 4-wave
-// workgroup per CU, each wave on its own tiles; fp32 X, F = 81, k = 4 (16-sample tiles) or k = 8
-// (8-sample tiles); W resident in LDS when the grid's share fits, else streamed with X).
-// CNMF_WT_PD = prefetch depth 2..4 of the k = 4 W-resident single-GPU kernel, 3..5 of the k = 8
-// streamed-W one (default 3).
-static int wt_pd(int k, bool wres, bool multi) {
-  const char* v = diag_env("CNMF_WT_PD");
-  const int pd = v ? atoi(v) : 3;
-  if (k == 4 && wres && !multi && pd >= 2 && pd <= 4) return pd;
-  if (k == 8 && !wres && !multi && pd >= 3 && pd <= 5) return pd;
-  return 3;
-}
-extern "C++" {
-template <int KK, bool WRES>
-static PassFn wt_fn_k(int pd, bool multi, bool tol) {
-  if (tol)  // the device tolerance test: PD = 3
-    return multi ? reinterpret_cast<PassFn>(&mu_iter_wt_kernel<KK, WRES, 3, true, true>)
-                 : reinterpret_cast<PassFn>(&mu_iter_wt_kernel<KK, WRES, 3, false, true>);
-  if (multi) return reinterpret_cast<PassFn>(&mu_iter_wt_kernel<KK, WRES, 3, true>);
-#ifdef CNMF_DIAG  // the prefetch-depth sweeps (CNMF_WT_PD): diagnostic build only
-  if (KK == 4 && WRES && pd == 2) return reinterpret_cast<PassFn>(&mu_iter_wt_kernel<4, true, 2, false>);
-  if (KK == 4 && WRES && pd == 4) return reinterpret_cast<PassFn>(&mu_iter_wt_kernel<4, true, 4, false>);
-  if (KK == 8 && !WRES && pd == 4) return reinterpret_cast<PassFn>(&mu_iter_wt_kernel<8, false, 4, false>);
-  if (KK == 8 && !WRES && pd == 5) return reinterpret_cast<PassFn>(&mu_iter_wt_kernel<8, false, 5, false>);
-#else
-  (void)pd;
-#endif
-  return reinterpret_cast<PassFn>(&mu_iter_wt_kernel<KK, WRES, 3, false>);
-}
-}
-// the k = 8 matrix-core wave tiles (layout 5): slower than the VALU wave tiles on every box measured
-// (DESIGN §3.0), so since round 6 they exist in the diagnostic build only (VERDICT r5 item 8); the
-// product refuses layout 5 with CNMF_ERR_ARG
-static PassFn mf8_fn(bool wres, bool multi, bool tol) {
-#ifndef CNMF_DIAG
-  (void)wres; (void)multi; (void)tol;
-  return nullptr;
-#else
-  if (wres)
-    return tol ? (multi ? reinterpret_cast<PassFn>(&mu_iter_mf8_kernel<true, 3, true, true>)
-                        : reinterpret_cast<PassFn>(&mu_iter_mf8_kernel<true, 3, false, true>))
-               : (multi ? reinterpret_cast<PassFn>(&mu_iter_mf8_kernel<true, 3, true, false>)
-                        : reinterpret_cast<PassFn>(&mu_iter_mf8_kernel<true, 3, false, false>));
-  return tol ? (multi ? reinterpret_cast<PassFn>(&mu_iter_mf8_kernel<false, 3, true, true>)
-                      : reinterpret_cast<PassFn>(&mu_iter_mf8_kernel<false, 3, false, true>))
-             : (multi ? reinterpret_cast<PassFn>(&mu_iter_mf8_kernel<false, 3, true, false>)
-                      : reinterpret_cast<PassFn>(&mu_iter_mf8_kernel<false, 3, false, false>));
-#endif
-}
-static PassFn wt_fn(int k, bool wres, bool multi, bool tol = false) {
-  const int pd = tol ? 3 : wt_pd(k, wres, multi);
-  if (k == 4) return wres ? wt_fn_k<4, true>(pd, multi, tol) : wt_fn_k<4, false>(pd, multi, tol);
-  return wres ? wt_fn_k<8, true>(pd, multi, tol) : wt_fn_k<8, false>(pd, multi, tol);
-}
-static int device_cus() {
-  static int cus[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-  if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus[dev] = 0;
-  return cus[dev];
-}
-struct WtLaunch {
-  PassFn fn;
-  int64_t G, n_tiles;
-  size_t lds;
-  bool mf;       // k = 8 on the matrix cores (mu_iter_mf8_kernel)
-  int nres = 0;  // W streamed: the first nres tiles of every wave resident in the LDS left over
-  bool wres = false;  // W resident (every tile)
-};
-// the wave-tile launch for this shape, or false (not eligible: another kernel serves it).  k = 4
-// follows the layout switch (variant 4, the default); k = 8 has no other persistent layout.
-static bool wt_plan(int64_t n_rows, int x_dtype, int F, int k, bool multi, int layout, WtLaunch* out,
-                    bool tol = false) {
-  if (x_dtype != CNMF_F32 || F != wt::F || (k != 4 && k != 8) || n_rows <= 0) return false;
-  if (k == 4 && layout != 4) return false;
-  if (k == 8 && layout != 4 && layout != 5) return false;
-  // k = 8, layout 4: the VALU wave tiles (8-sample tiles); layout 5 (rows a multiple of 16): the
-  // matrix-core wave tiles (16-sample tiles; slower than layout 4 on the MI355X measured)
-  const bool mf = k == 8 && layout == 5 && n_rows % 16 == 0;
-  const int tsw = mf ? 16 : 64 / k, wbw = tsw * k * 4;
-  if (n_rows % tsw != 0) return false;
-  const size_t l_wres = mf ? (size_t)wt::GeoMF8::L_WRES
-                           : (k == 4 ? (size_t)wt::Geo<4>::L_WRES : (size_t)wt::Geo<8>::L_WRES);
-  const int ncu = device_cus();
-  const int64_t n_tiles = n_rows / tsw;
-  for (int wres = 1; wres >= 0; --wres) {
-    const int pd = tol ? 3 : wt_pd(k, wres != 0, multi);
-    // tiles per wave: > PD (the first prefetches), >= 2·PD + 1 when W is streamed (re-load hazard)
-    const int min_nbt = wres ? pd + 1 : 2 * pd + 1;
-    int64_t G = std::min<int64_t>({(int64_t)ncu, n_tiles / (wt::NWV * min_nbt), (int64_t)sl::GROUP * sl::MAX_GROUPS});
-    if (const char* mg = diag_env("CNMF_WT_MAXG"))  // diagnostic: fewer, fuller waves (strong-scaling shards)
-      if (atoi(mg) > 0) G = std::min<int64_t>(G, atoi(mg));
-    if (G < 1) continue;
-    const int64_t nbt_max = (n_tiles + wt::NWV * G - 1) / (wt::NWV * G);
-    // W resident: the four waves' W tiles; TOL (the wave-tile kernel) a second copy: the snapshot of
-    // the checked state
-    size_t lds = l_wres + (wres ? (size_t)wt::NWV * nbt_max * wbw * (tol && !mf ? 2 : 1) : 0);
-    if (lds > kMaxLds) continue;
-    // W streamed (the VALU wave tiles): as many of each wave's tiles W-resident as the LDS holds —
-    // their W neither read nor written through HBM in the iterations (cfg3's shard: ~78 % of its W
-    // traffic).  CNMF_WT_NRES (diagnostic) caps it; 0 streams every tile.
-    int nres = 0;
-    if (!wres && !mf) {
-      int64_t cap = (int64_t)((kMaxLds - lds) / ((size_t)wt::NWV * wbw));
-      if (const char* nr = diag_env("CNMF_WT_NRES")) cap = std::min<int64_t>(cap, atoi(nr));
-      nres = (int)std::max<int64_t>(0, std::min<int64_t>(cap, nbt_max));
-      lds += (size_t)wt::NWV * nres * wbw;
-    }
-    const PassFn fn = mf ? mf8_fn(wres != 0, multi, tol) : wt_fn(k, wres != 0, multi, tol);
-    if (max_resident(fn, lds) < G) continue;  // the whole grid co-resident (cached query)
-    *out = WtLaunch{fn, G, n_tiles, lds, mf, nres, wres != 0};
-    return true;
-  }
-  return false;
-}
 // the weighted wave-tile launch for this shape, or false (not served: the per-iteration pass)
 struct WwLaunch {
   int64_t G, n_tiles;
@@ -8943,8 +7157,7 @@ static int als_iterations(int n_iter, const void* X, int x_dtype, void* W, doubl
                    (long long)n_rows, n_features, k);
   if (!X || !W || !H64 || !Ht || !HHt || !table || !partials || !stage || !counter || !AB)
     return set_err(CNMF_ERR_ARG, "null pointer argument");
-  if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(W) & 15))
-    return set_err(CNMF_ERR_ALIGN, "X and W must be 16-byte aligned");
+  if (int st = check_xw_aligned(X, W)) return st;
   if (!(sum_to_one >= 0.0) || !(smoothness >= 0.0)) return set_err(CNMF_ERR_ARG, "smoothness and sum_to_one must be >= 0");
   if (L.G > n_parts) return set_err(CNMF_ERR_ARG, "partials hold %lld rows, the persistent grid needs %lld",
                                     (long long)n_parts, (long long)L.G);
@@ -8971,10 +7184,12 @@ static int als_iterations(int n_iter, const void* X, int x_dtype, void* W, doubl
   pa.prio = diag_env("CNMF_ALS_PRIO") ? atoi(diag_env("CNMF_ALS_PRIO")) : 2;  // steps per ladder band
   pa.tolctl = tolctl;
   void* args[] = {&pa};
-  if (events && n_events >= 2) HIP_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(events[0]), hs));
-  HIP_CHECK(hipLaunchKernel(reinterpret_cast<const void*>(wa_fn(multi, tol)), dim3((unsigned)L.G), dim3(NT), args,
-                            L.lds, hs));
-  if (events && n_events >= 2) HIP_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(events[1]), hs));
+  const int st = with_events(events, n_events, hs, [&]() -> int {
+    HIP_CHECK(hipLaunchKernel(reinterpret_cast<const void*>(wa_fn(multi, tol)), dim3((unsigned)L.G), dim3(NT), args,
+                              L.lds, hs));
+    return CNMF_OK;
+  });
+  if (st) return st;
   // TOL: the iteration flag may still hold the last (or the stopping) iteration: cleared in stream order
   if (tol) HIP_CHECK(hipMemsetAsync(counter + CNT_FLAG, 0, sizeof(uint32_t), hs));
   return CNMF_OK;
@@ -9006,48 +7221,6 @@ int cnmf_als_iterations_multi(int n_iter, const void* X, int x_dtype, void* W, d
   if (!xctl && n_iter > 0) return set_err(CNMF_ERR_ARG, "null exchange control block");
   return als_iterations(n_iter, X, x_dtype, W, H64, Ht, HHt, table, partials, n_parts, stage, counter, AB, n_rows,
                         n_features, k, sum_to_one, smoothness, xctl, events, n_events, stream);
-}
-
-// the first reduction level through the XCD's L2 (PersistArgs::l2rows); CNMF_WT_L2ROWS in the
-// diagnostic build overrides the default
-static int wt_l2rows() {
-  const char* v = diag_env("CNMF_WT_L2ROWS");
-  return v ? (atoi(v) != 0) : 0;
-}
-static int launch_wt(const WtLaunch& L, int n_iter, const void* X, void* W, double* H64, double* Ht, double* HHt,
-                     double* partials, double* stage, uint32_t* counter, double* AB, double l1_W, double l2_W,
-                     double l1_H, double l2_H, int apply_first, int apply_last, hipStream_t s, uint64_t* xctl,
-                     double* tolctl = nullptr) {
-  if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(W) & 15))
-    return set_err(CNMF_ERR_ALIGN, "X and W must be 16-byte aligned");
-  PersistArgs pa;
-  pa.X = static_cast<const float*>(X);
-  pa.W = static_cast<float*>(W);
-  pa.H64 = H64;
-  pa.Ht = Ht;
-  pa.HHt = HHt;
-  pa.partials = partials;
-  pa.groups = stage;
-  pa.AB = AB;
-  pa.cnt = counter;
-  pa.n_tiles = L.n_tiles;
-  pa.n_iter = n_iter;
-  pa.n_groups = (int)((L.G + sl::GROUP - 1) / sl::GROUP);
-  if (const char* gz = diag_env("CNMF_WT_GROUP"))  // diagnostic: workgroups per first-level group
-    if (atoi(gz) > 0) pa.n_groups = (int)std::min<int64_t>((L.G + atoi(gz) - 1) / atoi(gz), sl::MAX_GROUPS);
-  pa.n_static = L.nres;
-  pa.l1W = l1_W;
-  pa.l2W = l2_W;
-  pa.l1H = l1_H;
-  pa.l2H = l2_H;
-  pa.apply_first = apply_first;
-  pa.apply_last = apply_last;
-  pa.xctl = xctl;
-  pa.tolctl = tolctl;
-  pa.l2rows = L.mf ? 0 : wt_l2rows();
-  void* args[] = {&pa};
-  HIP_CHECK(hipLaunchKernel(L.fn, dim3((unsigned)L.G), dim3(NT), args, L.lds, s));
-  return CNMF_OK;
 }
 
 int64_t cnmf_persist_workgroups(int64_t n_rows, int n_features, int k, int x_dtype, int layout, int multi) {
@@ -9227,28 +7400,8 @@ static int launch_persistent(int64_t G, int n_iter, const void* X, void* W, doub
                              int layout, uint64_t* xctl = nullptr) {
   if (G > n_parts) return set_err(CNMF_ERR_ARG, "partials hold %lld rows, the persistent grid needs %lld",
                                   (long long)n_parts, (long long)G);
-  PersistArgs pa;
-  pa.X = static_cast<const float*>(X);
-  pa.W = static_cast<float*>(W);
-  pa.H64 = H64;
-  pa.Ht = Ht;
-  pa.HHt = HHt;
-  pa.partials = partials;
-  pa.groups = stage;
-  pa.AB = AB;
-  pa.cnt = counter;
-  pa.n_tiles = n_rows / TS;
-  pa.n_iter = n_iter;
-  pa.n_groups = (int)((G + sl::GROUP - 1) / sl::GROUP);
-  pa.n_static = 0;
-  pa.l1W = l1_W;
-  pa.l2W = l2_W;
-  pa.l1H = l1_H;
-  pa.l2H = l2_H;
-  pa.apply_first = apply_first;
-  pa.apply_last = apply_last;
-  pa.xctl = xctl;
-  pa.tolctl = nullptr;
+  PersistArgs pa = persist_args(X, W, H64, Ht, HHt, partials, stage, counter, AB, n_rows / TS, n_iter, G, l1_W,
+                                l2_W, l1_H, l2_H, apply_first, apply_last, xctl, nullptr);
   const bool multi = xctl != nullptr;
   void* args[] = {&pa};
   if (n_iter > 1) {
@@ -9310,34 +7463,10 @@ int cnmf_mu_shard_step(const void* X, int x_dtype, void* W, double* H64, double*
     // is the multi-iteration launch's (wave tiles by default), so the RCCL path and the in-launch
     // exchange sum the same fp32 partials.
     if (!partials) return set_err(CNMF_ERR_ARG, "null pointer argument");
-    if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(W) & 15))
-      return set_err(CNMF_ERR_ALIGN, "X and W must be 16-byte aligned");
+    if (int st = check_xw_aligned(X, W)) return st;
     if (G > n_parts) return set_err(CNMF_ERR_ARG, "partials hold too few rows");
-    PersistArgs pa;
-    pa.X = static_cast<const float*>(X);
-    pa.W = static_cast<float*>(W);
-    pa.H64 = H64;
-    pa.Ht = Ht;
-    pa.HHt = HHt;
-    pa.partials = partials;
-    pa.groups = stage;
-    pa.AB = AB;
-    pa.cnt = counter;
-    pa.n_tiles = n_rows / TS;
-    pa.n_iter = 1;
-    pa.n_groups = (int)((G + sl::GROUP - 1) / sl::GROUP);
-    pa.n_static = 0;
-    pa.l1W = l1_W;
-    pa.l2W = l2_W;
-    pa.l1H = l1_H;
-    pa.l2H = l2_H;
-    pa.apply_first = apply_first;
-    pa.apply_last = 0;
-    pa.xctl = nullptr;
-    pa.tolctl = nullptr;
-    void* args[] = {&pa};
-    HIP_CHECK(hipLaunchKernel(persist_fn(), dim3((unsigned)G), dim3(NT), args, sl::L_PTOTAL, hs));
-    return CNMF_OK;
+    return launch_persistent(G, 1, X, W, H64, Ht, HHt, partials, n_parts, stage, counter, AB, n_rows, l1_W, l2_W,
+                             l1_H, l2_H, apply_first, 0, hs, layout);
   }
   int st;
   if (apply_first) {
@@ -9369,12 +7498,10 @@ int cnmf_mu_iterations(int n_iter, const void* X, int x_dtype, void* W, double* 
     if (wt_plan(n_rows, x_dtype, n_features, k, false, layout, &L) && L.G <= n_parts) {
       if (!X || !W || !H64 || !Ht || !HHt || !partials || !stage || !counter || !AB)
         return set_err(CNMF_ERR_ARG, "null pointer argument");
-      if (events && n_events >= 2) HIP_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(events[0]), hs));
-      const int st = launch_wt(L, n_iter, X, W, H64, Ht, HHt, partials, stage, counter, AB, l1_W, l2_W, l1_H,
-                               l2_H, 0, 1, hs, nullptr);
-      if (st) return st;
-      if (events && n_events >= 2) HIP_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(events[1]), hs));
-      return CNMF_OK;
+      return with_events(events, n_events, hs, [&] {
+        return launch_wt(L, n_iter, X, W, H64, Ht, HHt, partials, stage, counter, AB, l1_W, l2_W, l1_H, l2_H, 0, 1,
+                         hs, nullptr);
+      });
     }
   }
   {  // cfg4: the bf16 wave-tile pass with the reduction and the basis update in the launch
@@ -9382,8 +7509,7 @@ int cnmf_mu_iterations(int n_iter, const void* X, int x_dtype, void* W, double* 
     if (bwp_plan(n_rows, x_dtype, n_features, k, layout, &B) && B.G <= n_parts) {
       if (!X || !W || !H64 || !Ht || !HHt || !partials || !counter || !AB)
         return set_err(CNMF_ERR_ARG, "null pointer argument");
-      if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(W) & 15))
-        return set_err(CNMF_ERR_ALIGN, "X and W must be 16-byte aligned");
+      if (int st = check_xw_aligned(X, W)) return st;
       BfwArgs ba{};
       ba.X = static_cast<const bf16_t*>(X);
       ba.W = static_cast<float*>(W);
@@ -9406,11 +7532,11 @@ int cnmf_mu_iterations(int n_iter, const void* X, int x_dtype, void* W, double* 
       ba.l1H = l1_H;
       ba.l2H = l2_H;
       void* args[] = {&ba};
-      if (events && n_events >= 2) HIP_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(events[0]), hs));
-      HIP_CHECK(hipLaunchKernel(reinterpret_cast<const void*>(&mu_iter_bfw_kernel), dim3((unsigned)B.G), dim3(NT),
-                                args, B.lds, hs));
-      if (events && n_events >= 2) HIP_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(events[1]), hs));
-      return CNMF_OK;
+      return with_events(events, n_events, hs, [&]() -> int {
+        HIP_CHECK(hipLaunchKernel(reinterpret_cast<const void*>(&mu_iter_bfw_kernel), dim3((unsigned)B.G), dim3(NT),
+                                  args, B.lds, hs));
+        return CNMF_OK;
+      });
     }
   }
   const int64_t G = persist_grid(n_rows, x_dtype, n_features, k);
@@ -9418,14 +7544,11 @@ int cnmf_mu_iterations(int n_iter, const void* X, int x_dtype, void* W, double* 
   if (G > 0) {
     if (!X || !W || !H64 || !Ht || !HHt || !partials || !stage || !counter || !AB)
       return set_err(CNMF_ERR_ARG, "null pointer argument");
-    if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(W) & 15))
-      return set_err(CNMF_ERR_ALIGN, "X and W must be 16-byte aligned");
-    if (events && n_events >= 2) HIP_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(events[0]), hs));
-    int st = launch_persistent(G, n_iter, X, W, H64, Ht, HHt, partials, n_parts, stage, counter, AB,
-                               n_rows, l1_W, l2_W, l1_H, l2_H, 0, 1, hs, layout);
-    if (st) return st;
-    if (events && n_events >= 2) HIP_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(events[1]), hs));
-    return CNMF_OK;
+    if (int st = check_xw_aligned(X, W)) return st;
+    return with_events(events, n_events, hs, [&] {
+      return launch_persistent(G, n_iter, X, W, H64, Ht, HHt, partials, n_parts, stage, counter, AB, n_rows, l1_W,
+                               l2_W, l1_H, l2_H, 0, 1, hs, layout);
+    });
   }
   // events: 2·n_iter around each iteration (pass + reduction + update), or (n_events == 2) around the
   // whole n iterations — no event record between the launches of a timed stretch
@@ -9482,12 +7605,10 @@ int cnmf_mu_iterations_multi(int n_iter, const void* X, int x_dtype, void* W, do
     if (wt_plan(n_rows, x_dtype, n_features, k, true, layout, &L) && L.G <= n_parts) {
       if (!X || !W || !H64 || !Ht || !HHt || !partials || !stage || !counter || !AB || !xctl)
         return set_err(CNMF_ERR_ARG, "null pointer argument");
-      if (events && n_events >= 2) HIP_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(events[0]), hs));
-      const int st = launch_wt(L, n_iter, X, W, H64, Ht, HHt, partials, stage, counter, AB, l1_W, l2_W, l1_H,
-                               l2_H, 0, 1, hs, xctl);
-      if (st) return st;
-      if (events && n_events >= 2) HIP_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(events[1]), hs));
-      return CNMF_OK;
+      return with_events(events, n_events, hs, [&] {
+        return launch_wt(L, n_iter, X, W, H64, Ht, HHt, partials, stage, counter, AB, l1_W, l2_W, l1_H, l2_H, 0, 1,
+                         hs, xctl);
+      });
     }
   }
   const int64_t G = persist_grid(n_rows, x_dtype, n_features, k, true);
@@ -9495,14 +7616,11 @@ int cnmf_mu_iterations_multi(int n_iter, const void* X, int x_dtype, void* W, do
   if (G == 0) return set_err(CNMF_ERR_UNSUPPORTED, "the in-launch multi-GPU path serves the persistent shapes only");
   if (!X || !W || !H64 || !Ht || !HHt || !partials || !stage || !counter || !AB || !xctl)
     return set_err(CNMF_ERR_ARG, "null pointer argument");
-  if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(W) & 15))
-    return set_err(CNMF_ERR_ALIGN, "X and W must be 16-byte aligned");
-  if (events && n_events >= 2) HIP_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(events[0]), hs));
-  int st = launch_persistent(G, n_iter, X, W, H64, Ht, HHt, partials, n_parts, stage, counter, AB,
-                             n_rows, l1_W, l2_W, l1_H, l2_H, 0, 1, hs, layout, xctl);
-  if (st) return st;
-  if (events && n_events >= 2) HIP_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(events[1]), hs));
-  return CNMF_OK;
+  if (int st = check_xw_aligned(X, W)) return st;
+  return with_events(events, n_events, hs, [&] {
+    return launch_persistent(G, n_iter, X, W, H64, Ht, HHt, partials, n_parts, stage, counter, AB, n_rows, l1_W,
+                             l2_W, l1_H, l2_H, 0, 1, hs, layout, xctl);
+  });
 }
 
 
@@ -9524,11 +7642,11 @@ int cnmf_mu_fit_tol(int max_iter, const void* X, int x_dtype, void* W, double* H
                                     (long long)n_parts, (long long)L.G);
   if (!X || !W || !H64 || !Ht || !HHt || !partials || !stage || !counter || !AB || !tolctl)
     return set_err(CNMF_ERR_ARG, "null pointer argument");
-  if (events && n_events >= 2) HIP_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(events[0]), hs));
-  const int st = launch_wt(L, max_iter, X, W, H64, Ht, HHt, partials, stage, counter, AB, l1_W, l2_W, l1_H, l2_H,
-                           0, 1, hs, xctl, tolctl);
+  const int st = with_events(events, n_events, hs, [&] {
+    return launch_wt(L, max_iter, X, W, H64, Ht, HHt, partials, stage, counter, AB, l1_W, l2_W, l1_H, l2_H, 0, 1,
+                     hs, xctl, tolctl);
+  });
   if (st) return st;
-  if (events && n_events >= 2) HIP_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(events[1]), hs));
   // the iteration flag may still hold the last (or the stopping) iteration: cleared in stream order
   HIP_CHECK(hipMemsetAsync(counter + CNT_FLAG, 0, sizeof(uint32_t), hs));
   return CNMF_OK;
@@ -9617,10 +7735,10 @@ static int wmu_iterations(int n_iter, const float* X, const float* M, float* W, 
   void* args[] = {&pa};
   const void* fn = multi ? reinterpret_cast<const void*>(&wmu_iter_wt_kernel<2, true>)
                          : reinterpret_cast<const void*>(&wmu_iter_wt_kernel<2>);
-  if (events && n_events >= 2) HIP_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(events[0]), hs));
-  HIP_CHECK(hipLaunchKernel(fn, dim3((unsigned)L.G), dim3(NT), args, L.lds, hs));
-  if (events && n_events >= 2) HIP_CHECK(hipEventRecord(reinterpret_cast<hipEvent_t>(events[1]), hs));
-  return CNMF_OK;
+  return with_events(events, n_events, hs, [&]() -> int {
+    HIP_CHECK(hipLaunchKernel(fn, dim3((unsigned)L.G), dim3(NT), args, L.lds, hs));
+    return CNMF_OK;
+  });
 }
 
 int cnmf_wmu_iterations(int n_iter, const float* X, const float* M, float* W, double* H64, double* partials,
@@ -9649,89 +7767,14 @@ int cnmf_wmu_basis_update(const double* AD, double* H64, int n_features, int k, 
   return CNMF_OK;
 }
 
-// ---- GPU NNDSVD initialisation; see ig_gram_kernel
-static int ig_blocks(int64_t n_rows) {
-  const int ncu = device_cus();
-  const int64_t want = (n_rows + 4095) / 4096;  // >= 4096 rows (64 tiles) per workgroup
-  return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, 2 * (int64_t)std::max(ncu, 1)), 1024));
-}
-int64_t cnmf_init_gram_rows(int64_t n_rows) { return n_rows > 0 ? ig_blocks(n_rows) : 0; }
-
-int cnmf_init_gram(const void* X, int x_dtype, int64_t n_rows, int n_features, double* partials,
-                   int64_t n_parts, void* stream) {
-  if (!X || !partials) return set_err(CNMF_ERR_ARG, "null pointer argument");
-  if (n_rows < 1 || n_features < 1 || n_features > ig::FP)
-    return set_err(CNMF_ERR_UNSUPPORTED, "GPU init: n_features=%d (1..%d), n_rows=%lld", n_features, ig::FP, (long long)n_rows);
-  const int G = ig_blocks(n_rows);
-  if (G > n_parts) return set_err(CNMF_ERR_ARG, "partials hold %lld rows, the pass needs %d", (long long)n_parts, G);
-  const int64_t rpb = (n_rows + G - 1) / G;
-  const size_t lds = (size_t)ig::GT * ig::FP * 8;
-  hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
-  switch (x_dtype) {
-    case CNMF_F32: hipLaunchKernelGGL(ig_gram_kernel<float>, dim3(G), dim3(256), lds, hs, static_cast<const float*>(X), n_rows, n_features, rpb, partials); break;
-    case CNMF_F64: hipLaunchKernelGGL(ig_gram_kernel<double>, dim3(G), dim3(256), lds, hs, static_cast<const double*>(X), n_rows, n_features, rpb, partials); break;
-    case CNMF_BF16: hipLaunchKernelGGL(ig_gram_kernel<bf16_t>, dim3(G), dim3(256), lds, hs, static_cast<const bf16_t*>(X), n_rows, n_features, rpb, partials); break;
-    default: return set_err(CNMF_ERR_ARG, "x_dtype %d", x_dtype);
-  }
-  HIP_CHECK(hipGetLastError());
-  return CNMF_OK;
-}
-
-int cnmf_init_xm(const void* X, int x_dtype, int64_t n_rows, int n_features, int k, const double* M, double* U,
-                 void* stream) {
-  if (!X || !M || !U) return set_err(CNMF_ERR_ARG, "null pointer argument");
-  if (n_rows < 1 || n_features < 1 || n_features > ig::FP || k < 1 || k > ig::KMAX)
-    return set_err(CNMF_ERR_UNSUPPORTED, "GPU init: n_features=%d (1..%d), k=%d (1..%d)", n_features, ig::FP, k, ig::KMAX);
-  const int ncu = device_cus();
-  const int64_t n_tiles = (n_rows + ig::GT - 1) / ig::GT;
-  const int G = (int)std::max<int64_t>(1, std::min<int64_t>(n_tiles, 4 * (int64_t)std::max(ncu, 1)));
-  const size_t lds = (size_t)ig::FP * ig::KMAX * 8 + (size_t)ig::GT * (n_features + 1) * 8;
-  hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
-  switch (x_dtype) {
-    case CNMF_F32: hipLaunchKernelGGL(ig_xm_kernel<float>, dim3(G), dim3(256), lds, hs, static_cast<const float*>(X), n_rows, n_features, k, M, U); break;
-    case CNMF_F64: hipLaunchKernelGGL(ig_xm_kernel<double>, dim3(G), dim3(256), lds, hs, static_cast<const double*>(X), n_rows, n_features, k, M, U); break;
-    case CNMF_BF16: hipLaunchKernelGGL(ig_xm_kernel<bf16_t>, dim3(G), dim3(256), lds, hs, static_cast<const bf16_t*>(X), n_rows, n_features, k, M, U); break;
-    default: return set_err(CNMF_ERR_ARG, "x_dtype %d", x_dtype);
-  }
-  HIP_CHECK(hipGetLastError());
-  return CNMF_OK;
-}
-
-int64_t cnmf_init_stats_rows(int64_t n_rows) { return n_rows > 0 ? ig_blocks(n_rows) : 0; }
-
-int cnmf_init_stats(const double* U, int64_t n_rows, int k, double* out, int64_t n_parts, void* stream) {
-  if (!U || !out) return set_err(CNMF_ERR_ARG, "null pointer argument");
-  if (n_rows < 1 || k < 1 || k > ig::KMAX) return set_err(CNMF_ERR_SHAPE, "invalid shape");
-  const int G = ig_blocks(n_rows);
-  if (G > n_parts) return set_err(CNMF_ERR_ARG, "out holds %lld rows, the pass needs %d", (long long)n_parts, G);
-  const int64_t rpb = (n_rows + G - 1) / G;
-  hipLaunchKernelGGL(ig_stats_kernel, dim3(G), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), U, n_rows, k, rpb, out);
-  HIP_CHECK(hipGetLastError());
-  return CNMF_OK;
-}
-
-int cnmf_init_fill(const double* U, int64_t n_rows, int k, const double* coef, const int* part, const double* sgn,
-                   double eps, double fill, void* W, int w_dtype, void* stream) {
-  if (!U || !coef || !part || !sgn || !W) return set_err(CNMF_ERR_ARG, "null pointer argument");
-  if (n_rows < 1 || k < 1 || k > ig::KMAX) return set_err(CNMF_ERR_SHAPE, "invalid shape");
-  const int ncu = device_cus();
-  const int G = (int)std::max<int64_t>(1, std::min<int64_t>((n_rows * k + 255) / 256, 8 * (int64_t)std::max(ncu, 1)));
-  hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
-  if (w_dtype == CNMF_F32)
-    hipLaunchKernelGGL(ig_fill_kernel<float>, dim3(G), dim3(256), 0, hs, U, n_rows, k, coef, part, sgn, eps, fill, static_cast<float*>(W));
-  else if (w_dtype == CNMF_F64)
-    hipLaunchKernelGGL(ig_fill_kernel<double>, dim3(G), dim3(256), 0, hs, U, n_rows, k, coef, part, sgn, eps, fill, static_cast<double*>(W));
-  else
-    return set_err(CNMF_ERR_ARG, "w_dtype %d", w_dtype);
-  HIP_CHECK(hipGetLastError());
-  return CNMF_OK;
-}
 }  // extern "C"
 
-#ifdef CNMF_PD_PROBE
-// diagnostic (tools/audit_wt_asm.py): the k = 8 streamed-W wave-tile kernel at a
-// prefetch depth the product never launches, compiled only to inspect its ISA
-namespace cnmf {
-template __global__ void mu_iter_wt_kernel<8, false, CNMF_PD_PROBE, false, false>(PersistArgs);
-}
+
+// The families that have a file of their own.  This file is two things until the last family has
+// moved out: compiled with -DCNMF_SEPARATE it is the object of the families still in it
+// (cnmf_amd/build.py links it with the others'); compiled without, it is the whole library as one
+// translation unit (the stamps variant, tests/asan/build.sh, the -S listings of tools/).
+#ifndef CNMF_SEPARATE
+#include "wt.hip"
+#include "init.hip"
 #endif

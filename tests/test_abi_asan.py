@@ -4,6 +4,7 @@ available on this pool) and linked into tests/asan/abi_asan_main.cpp, which driv
 point's argument checks without a GPU (null pointers, bad shapes / dtypes / layouts / worlds, the
 bounded error message).  The binary is cached under build/asan and rebuilt when a source is newer
 (the host-sanitized build takes ~2.5 min)."""
+import glob
 import os
 import subprocess
 
@@ -12,8 +13,9 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "build", "asan")
 BIN = os.path.join(OUT, "abi_asan")
-SRCS = [os.path.join(ROOT, "cnmf_amd", "csrc", "cnmf_hip.hip"), os.path.join(ROOT, "include", "cnmf_hip.h"),
-        os.path.join(ROOT, "tests", "asan", "abi_asan_main.cpp"), os.path.join(ROOT, "tests", "asan", "build.sh")]
+SRCS = sorted(glob.glob(os.path.join(ROOT, "cnmf_amd", "csrc", "*"))) + [
+    os.path.join(ROOT, "include", "cnmf_hip.h"), os.path.join(ROOT, "tests", "asan", "abi_asan_main.cpp"),
+    os.path.join(ROOT, "tests", "asan", "build.sh")]
 
 
 def _stale():

@@ -13,13 +13,14 @@ is checked here, from the library file itself:
 
     python tools/kcheck.py [cnmf_amd/libcnmf_hip.so] [--arch gfx950] [--llvm DIR]
 
-Extracts the gfx950 code object (llvm-objcopy .hip_fatbin, clang-offload-bundler), disassembles it
-(llvm-objdump) and, per kernel whose name matches the wave-tile families, collects the AGPRs that
-are destinations of `global_load_dwordx4 a[..]` and lists every other instruction that reads or
-writes one of them (besides the `ds_write_b128` / `ds_write_b64` staging stores from them and
-`s_waitcnt`), plus any `vmcnt` immediate
-above the 6-bit field.  Exit status 1 on a finding; 2 when the check itself could not run (LLVM
-tools missing, no code object for the arch) — reported apart from findings.  The arch
+Extracts the gfx950 code objects (llvm-objcopy .hip_fatbin; one offload bundle per linked object,
+each through clang-offload-bundler), disassembles them (llvm-objdump) and, per kernel whose name
+matches the wave-tile families, collects the AGPRs that are destinations of
+`global_load_dwordx4 a[..]` and lists every other instruction that reads or writes one of them
+(besides the `ds_write_b128` / `ds_write_b64` staging stores from them and `s_waitcnt`), plus any
+`vmcnt` immediate above the 6-bit field.  Exit status 1 on a finding; 2 when the check itself could
+not run (LLVM tools missing, no code object for the arch) — reported apart from findings (ADVICE
+r5).  The arch
 defaults to CNMF_OFFLOAD_ARCH (the build's) or gfx950; the LLVM tools are taken from --llvm, else
 next to the hipcc the build used (HIPCC / <rocm>/lib/llvm/bin), else /opt/rocm/lib/llvm/bin.
 """
@@ -51,11 +52,13 @@ class ToolError(RuntimeError):
     """The check could not run (not a finding)."""
 FAMILIES = re.compile(r"(mu_iter_wt_kernel|mu_iter_mf8_kernel|wmu_iter_wt_kernel|als_iter_wt_kernel|"
                       r"mu_pass_bfw_kernel|mu_iter_bfw_kernel)")
+BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 OK_OPS = ("global_load_dwordx4", "ds_write_b128", "ds_write_b64", "s_waitcnt")
 
 
 def disassemble(lib: str, arch: str = "gfx950", llvm: str = LLVM) -> str:
-    """The `arch` code object of `lib`, disassembled; ToolError when a tool is missing or fails."""
+    """Every `arch` code object of `lib`, disassembled (concatenated, then NOTES_MARK and their notes);
+    ToolError when a tool is missing or fails."""
     def run(cmd, **kw):
         if not os.path.exists(cmd[0]):
             raise ToolError(f"{cmd[0]} not found (pass --llvm DIR)")
@@ -65,16 +68,28 @@ def disassemble(lib: str, arch: str = "gfx950", llvm: str = LLVM) -> str:
             raise ToolError(f"{os.path.basename(cmd[0])} failed ({r.returncode}): {err.strip()[-500:]}")
         return r
     with tempfile.TemporaryDirectory() as d:
-        fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "dev.co")
+        fat = os.path.join(d, "fat.bin")
         run([f"{llvm}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", lib, os.devnull])
-        run([f"{llvm}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}",
-             f"--targets=hipv4-amdgcn-amd-amdhsa--{arch}", f"--output={co}"])
-        if not os.path.exists(co) or os.path.getsize(co) == 0:
-            raise ToolError(f"{lib} holds no {arch} code object")
-        dis = run([f"{llvm}/llvm-objdump", "-d", "--no-show-raw-insn", co], text=True).stdout
+        # a library linked from several objects holds one offload bundle per object, one after
+        # another; the bundler reads only the first of a file, so each is cut out at its magic
+        data = open(fat, "rb").read()
+        starts = [m.start() for m in re.finditer(re.escape(BUNDLE_MAGIC), data)] or [0]
+        dis, notes = [], []
         readelf = f"{llvm}/llvm-readelf"
-        notes = run([readelf, "--notes", co], text=True).stdout if os.path.exists(readelf) else ""
-        return dis + "\n" + NOTES_MARK + "\n" + notes
+        for i, (a, b) in enumerate(zip(starts, starts[1:] + [len(data)])):
+            part, co = os.path.join(d, f"fat{i}.bin"), os.path.join(d, f"dev{i}.co")
+            with open(part, "wb") as f:
+                f.write(data[a:b])
+            run([f"{llvm}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={part}",
+                 f"--targets=hipv4-amdgcn-amd-amdhsa--{arch}", f"--output={co}"])
+            if not os.path.exists(co) or os.path.getsize(co) == 0:
+                continue
+            dis.append(run([f"{llvm}/llvm-objdump", "-d", "--no-show-raw-insn", co], text=True).stdout)
+            if os.path.exists(readelf):
+                notes.append(run([readelf, "--notes", co], text=True).stdout)
+        if not dis:
+            raise ToolError(f"{lib} holds no {arch} code object")
+        return "\n".join(dis) + "\n" + NOTES_MARK + "\n" + "\n".join(notes)
 
 
 NOTES_MARK = "=== kcheck: code object notes ==="
