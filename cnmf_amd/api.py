@@ -9,7 +9,7 @@ scikit-learn 1.7.2's Frobenius MU path (SK = sklearn/decomposition/_nmf.py):
   _initialize_nmf ('random')    SK:303-314   (nndsvd / nndsvda / nndsvdar: cnmf_amd.init)
 
 Differences, all deliberate: the solvers are 'mu' (the default here; sklearn's default 'cd'
-raises) and the build's constrained ALS 'als' (sum_to_one / smoothness; k ≤ 4),
+raises) and the build's constrained ALS 'als' (sum_to_one / smoothness; k ≤ 8),
 only beta_loss='frobenius' is accepted, sparse X is not, and n_components ≤ 16.  normalise=
 ('l1' | 'l2' | 'max') adds the §8 a6 projection (off by default, so 'mu' output is sklearn's).  NumPy
 inputs are copied to the GPU and results come back as NumPy arrays of X's dtype; torch tensors on a
@@ -301,8 +301,8 @@ def _resolve(X, W, H, n_components, init, update_H, alpha_W, alpha_H, l1_ratio, 
     k = int(k)
     if k > 16:
         raise ValueError(f"n_components={k} is not supported: the MI355X kernels handle 1..16.")
-    if solver == "als" and k > 4:
-        raise ValueError(f"n_components={k} is not supported by solver='als' (1..4).")
+    if solver == "als" and k > 8:
+        raise ValueError(f"n_components={k} is not supported by solver='als' (1..8).")
     if Mw is not None and k > 8:
         raise ValueError(f"n_components={k} is not supported by the weighted MU (1..8).")
     regs = _compute_regularization(n_samples, n_features, alpha_W, alpha_H, l1_ratio)
@@ -408,7 +408,7 @@ def factorise(X, W=None, H=None, n_components="auto", *, init=None, update_H=Tru
     `normalise` ('l1' | 'l2' | 'max' | None, default None = sklearn's output): after the fit, every
     row of H is scaled to unit norm and the scale folded into W's column (W·H unchanged;
     SURVEY.md §8 a6).
-    solver='als' selects the constrained ALS (k <= 4): per sample the exact
+    solver='als' selects the constrained ALS (k <= 8): per sample the exact
     non-negative least squares with a sum-to-one penalty of weight `sum_to_one` (δ; None = off),
     and per basis row the exact NNLS with a second-difference smoothness penalty `smoothness` (λ)
     — see oracle/als_ref.py for the precise objective.  tol / max_iter work as for 'mu'.

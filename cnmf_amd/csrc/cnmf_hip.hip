@@ -4,6 +4,7 @@
 //   persist.hpp  what the persistent launches share: counter map, PersistArgs, control blocks,
 //                sc1 helpers, in-launch reduction and exchange
 //   wt.hpp       wave-tile geometry and device helpers of the wave-tile kernels
+//   fcls8.hpp    the constrained-ALS W-step for 5 <= k <= 8 (device functions; inlined by the pass below)
 //   wt.hip       mu_iter_wt_kernel, wt_plan, launch_wt
 //   init.hip     GPU NNDSVD initialisation
 //   this file    the families not yet in a file of their own (pass, bf16, sample-lane, mf8, reductions
@@ -40,6 +41,7 @@
 //    addresses.
 #include "wt.hpp"
 #include "host.hpp"
+#include "fcls8.hpp"
 
 namespace cnmf {
 
@@ -331,6 +333,36 @@ __device__ __forceinline__ void phase12(const TX* __restrict__ sX, const TC* __r
       return;
     }
   }
+  if constexpr (KP == 8 && ALS) {
+    // ---- constrained-ALS W-step for 5 <= k <= 8 (fcls8.hpp): block principal pivoting per sample on
+    // the quad; sHHt holds Q = HHᵀ + δ²11ᵀ (stride 8, zero beyond k), l1 carries δ².  Lane qtr owns
+    // components qtr and qtr + 4; the start set is the old W's support (empty for a sample past the
+    // tile's end, whose c is zeroed: it ends at w = 0 in one trip).
+    const bool live = s < ns;
+    unsigned P0 = 0u;
+#pragma unroll
+    for (int j = 0; j < KP; ++j)
+      if (live && j < k && sW[s * k + j] > TC(0)) P0 |= 1u << j;
+    double cq[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const double cj = qtr == 0 ? p[4 * u] : (qtr == 1 ? p[4 * u + 1] : (qtr == 2 ? p[4 * u + 2] : p[4 * u + 3]));
+      cq[u] = (live && qtr + 4 * u < k) ? cj + l1 : 0.0;
+    }
+    double wm[2];
+    fcls8::solve_quad(cq, sHHt, P0, k, qtr, wm);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int j = qtr + 4 * u;
+      TC wn = TC(0);
+      if (live && j < k) {
+        wn = (TC)fmax(wm[u], 0.0);
+        W[(size_t)(tile * TS + s) * k + j] = wn;
+      }
+      sWn[s * KP + j] = wn;
+    }
+    return;
+  }
   double wr[KP];
 #pragma unroll
   for (int m = 0; m < KP; ++m)
@@ -374,15 +406,16 @@ __device__ __forceinline__ void phase12(const TX* __restrict__ sX, const TC* __r
 // ------------------------------------------------------------------------------------------------
 // minimum waves per SIMD the register allocator must leave room for (no spills; measured with
 // -Rpass-analysis=kernel-resource-usage): the F=81 fp32 k<=4 kernel fits 128 VGPRs (4 waves/SIMD)
-template <typename TX, int KP, int FT>
+template <typename TX, int KP, int FT, bool ALS = false>
 constexpr int pass_min_waves() {
+  if (KP == 8 && ALS) return sizeof(TX) == 8 ? 1 : 2;  // + the quad's 8x9 system (fcls8.hpp)
   return FT == 0 ? ((KP == 16 || sizeof(TX) == 8) ? 1 : 2)
                  : (KP == 4 ? (sizeof(TX) == 8 ? 3 : 4)
                             : (KP == 8 ? (sizeof(TX) == 8 ? 2 : 3) : (sizeof(TX) == 8 ? 1 : 2)));
 }
 
 template <typename TX, int KP, int FT, int NPW, bool SPLIT, bool ALS = false>
-__global__ __launch_bounds__(NT, (pass_min_waves<TX, KP, FT>())) void mu_pass_kernel(const TX* __restrict__ X,
+__global__ __launch_bounds__(NT, (pass_min_waves<TX, KP, FT, ALS>())) void mu_pass_kernel(const TX* __restrict__ X,
                                                      typename Compute<TX>::T* __restrict__ W,
                                                      const double* __restrict__ Ht,
                                                      const double* __restrict__ HHt,
@@ -413,7 +446,8 @@ __global__ __launch_bounds__(NT, (pass_min_waves<TX, KP, FT>())) void mu_pass_ke
   const bool do_loss = (flags & CNMF_PASS_LOSS) != 0;
   // basis-side constants into LDS once per launch (Ht zero-padded to 4q rows)
   for (int e = t; e < NWAVE * q * KP; e += NT) sHt[e] = e < F * KP ? (TH)Ht[e] : TH(0);
-  const int n_hht = ALS ? ALS_TAB : KP * KP;  // HHt, or the ALS passive-set table
+  // HHt; the ALS passive-set table (KP = 4); Q of the pivoting W-step (KP = 8, in the table buffer)
+  const int n_hht = (ALS && KP == 4) ? ALS_TAB : KP * KP;
   for (int e = t; e < n_hht; e += NT) sHHt[e] = HHt[e];
   if (t < 4) {
     sX[TS * F + t] = TX{};
@@ -3740,18 +3774,23 @@ __global__ __launch_bounds__(256) void scale_columns_kernel(TC* __restrict__ W, 
 //     pivoting, scattered to 4x4 (zeros outside P), and a valid flag (pivot > 1e-13·max diag).
 // ------------------------------------------------------------------------------------------------
 constexpr int ALS_MAX_F = 512;
-// components of the constrained ALS: the W-step's passive-set table (16 masks), the one-wave H-step's
-// running right-hand-side update and its sweep-count slots are sized for it; every ALS entry point
-// refuses k > ALS_MAX_K with CNMF_ERR_UNSUPPORTED before any launch
-constexpr int ALS_MAX_K = 4;
+// components of the constrained ALS: every ALS entry point refuses k > ALS_MAX_K with
+// CNMF_ERR_UNSUPPORTED before any launch.  k <= ALS_TABLE_K: the W-step's passive-set
+// table (16 masks) and the persistent launches, whose inlined one-wave H-step unrolls its running
+// right-hand-side update for ALS_TABLE_K rows; above it the pivoting W-step (fcls8.hpp) and the
+// per-iteration launches (the H-step of als_basis_kernel updates rows 4..7 in a runtime loop).
+// F: what als_lds_bytes(F, k) fits in kMaxLds — 512 up to k = 4, 480 at k = 8 (340·F + 640 bytes)
+constexpr int ALS_MAX_K = 8;
+constexpr int ALS_TABLE_K = 4;
 
 __host__ __device__ inline size_t als_pre_offset(int F, int k) {  // 16-B aligned, after the ints
   return (((size_t)2 * k * F + k * k + 9 * (size_t)F) * 8 + (3 * (size_t)F + 16) * 4 + 15) / 16 * 16;
 }
 __host__ __device__ inline size_t als_lds_bytes(int F, int k) {
   // doubles: A, H [k][F]; B [k][k]; b, x, d0, e1, e2, L0, L1, L2, z [F]; then ints: pas, inf, idx [F], 8;
-  // then (the one-wave form's per-row constants, round 5) bpre, rinv [k][F] and ALS_MAX_K sweep counts
-  return als_pre_offset(F, k) + ((size_t)2 * k * F + ALS_MAX_K) * 8;
+  // then (the one-wave form's per-row constants, round 5) bpre, rinv [k][F] and the sweep counts
+  // (ALS_TABLE_K slots up to that k: the persistent launches' size is unchanged; else ALS_MAX_K)
+  return als_pre_offset(F, k) + ((size_t)2 * k * F + (k <= ALS_TABLE_K ? ALS_TABLE_K : ALS_MAX_K)) * 8;
 }
 
 // M(fa, fb) of the row Hessian for |fa - fb| <= 2 (0 otherwise), fb < fa
@@ -4314,7 +4353,7 @@ __device__ __forceinline__ void als_hstep_wave(unsigned char* smem, int F, int k
       // the later rows' right-hand sides take this row's new values (each lane its own features:
       // the later read is the same lane's, in order)
 #pragma unroll
-      for (int m = 1; m < ALS_MAX_K; ++m)  // k <= ALS_MAX_K (every ALS entry point checks it)
+      for (int m = 1; m < ALS_TABLE_K; ++m)  // unrolled for the persistent kernels' k <= ALS_TABLE_K
         if (m > j && m < k) {
 #pragma unroll
           for (int c = 0; c < 2; ++c) {
@@ -4322,6 +4361,13 @@ __device__ __forceinline__ void als_hstep_wave(unsigned char* smem, int F, int k
             if (f < F) bpre[m * F + f] -= sB[m * k + j] * xnew[c];
           }
         }
+      for (int m = max(j + 1, ALS_TABLE_K); m < k; ++m) {  // rows 4..7 (als_basis_kernel at k > 4)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          const int f = 2 * lane + c;
+          if (f < F) bpre[m * F + f] -= sB[m * k + j] * xnew[c];
+        }
+      }
       lds_order();
     }
   }
@@ -4435,9 +4481,15 @@ __global__ __launch_bounds__(RED_NT) void als_basis_kernel(const double* __restr
     for (int e = t; e < k * F; e += RED_NT) H64[e] = sH[e];
     __syncthreads();  // workgroup-scope fence + barrier: the H64 stores are visible to this workgroup
   }
-  // Ht / HHt of the (new) H, then the passive-set table of the next W-step
+  // Ht / HHt of the (new) H, then for the next W-step the passive-set table (k <= 4) or, for the
+  // pivoting W-step, Q = HHᵀ + δ²11ᵀ itself in the table's first KP·KP doubles (zero beyond k)
   basis_update_block(nullptr, H64, Ht, HHt, F, k, KP, 0.0, 0.0, 0, nullptr, reinterpret_cast<double*>(smem));
   __syncthreads();
+  if (k > ALS_TABLE_K) {
+    for (int e = t; e < KP * KP; e += RED_NT)
+      table[e] = (e / KP < k && e % KP < k) ? HHt[e] + delta2 : 0.0;
+    return;
+  }
   als_table(HHt, KP, k, delta2, table, t);
 }
 
@@ -4638,22 +4690,27 @@ static PassKernel make_pk() {
                     sizeof(TX), sizeof(typename Compute<TX>::T)};
 }
 
-template <typename TX, int FT, int NPW, bool SPLIT>
+template <typename TX, int KP, int FT, int NPW, bool SPLIT>
 static PassKernel make_pk_als() {
-  return PassKernel{reinterpret_cast<PassFn>(&mu_pass_kernel<TX, 4, FT, NPW, SPLIT, true>), 4, NPW, SPLIT,
+  return PassKernel{reinterpret_cast<PassFn>(&mu_pass_kernel<TX, KP, FT, NPW, SPLIT, true>), KP, NPW, SPLIT,
                     sizeof(TX), sizeof(typename Compute<TX>::T)};
 }
 
-// the constrained-ALS W-step pass (k <= 4): the VALU pass kernel with the ALS phase 2 and fp64 Ht
-template <typename TX>
-static bool pick_als_tx(int F, int np, PassKernel* out) {
-  if (F == 81 && np == 2) { *out = make_pk_als<TX, 81, 2, true>(); return true; }  // IOP grid (cfg5)
-  if (np <= 1) { *out = make_pk_als<TX, 0, 1, true>(); return true; }
-  if (np == 2) { *out = make_pk_als<TX, 0, 2, true>(); return true; }
+// the constrained-ALS W-step pass: the VALU pass kernel with the ALS phase 2 and fp64 Ht (KP = 4: the
+// passive-set table, k <= 4; KP = 8: block principal pivoting per sample, 5 <= k <= 8)
+template <typename TX, int KP>
+static bool pick_als_kp(int F, int np, PassKernel* out) {
+  if (F == 81 && np == 2) { *out = make_pk_als<TX, KP, 81, 2, true>(); return true; }  // IOP grid (cfg5)
+  if (np <= 1) { *out = make_pk_als<TX, KP, 0, 1, true>(); return true; }
+  if (np == 2) { *out = make_pk_als<TX, KP, 0, 2, true>(); return true; }
   const int npw = (np + NWAVE - 1) / NWAVE;
-  if (npw <= 2) { *out = make_pk_als<TX, 0, 2, false>(); return true; }
-  if (npw <= 4) { *out = make_pk_als<TX, 0, 4, false>(); return true; }
+  if (npw <= 2) { *out = make_pk_als<TX, KP, 0, 2, false>(); return true; }
+  if (npw <= 4) { *out = make_pk_als<TX, KP, 0, 4, false>(); return true; }
   return false;
+}
+template <typename TX>
+static bool pick_als_tx(int KP, int F, int np, PassKernel* out) {
+  return KP == 4 ? pick_als_kp<TX, 4>(F, np, out) : pick_als_kp<TX, 8>(F, np, out);
 }
 
 template <typename TX, int KP>
@@ -6705,12 +6762,13 @@ static int als_basis_launch(const double* AB, double* H64, double* Ht, double* H
   if (k > ALS_MAX_K) return set_err(CNMF_ERR_UNSUPPORTED, "constrained ALS supports k <= %d (got %d)", ALS_MAX_K, k);
   if (F > ALS_MAX_F) return set_err(CNMF_ERR_UNSUPPORTED, "constrained ALS supports F <= %d", ALS_MAX_F);
   if (!(lam >= 0.0) || !(delta >= 0.0)) return set_err(CNMF_ERR_ARG, "smoothness and sum_to_one must be >= 0");
-  const size_t lds = std::max(als_lds_bytes(F, k), update_lds_doubles(F, k, 4) * sizeof(double));
+  const int KP = padded_k(k);
+  const size_t lds = std::max(als_lds_bytes(F, k), update_lds_doubles(F, k, KP) * sizeof(double));
   if (lds > kMaxLds) return set_err(CNMF_ERR_UNSUPPORTED, "basis too large for the ALS update");
   if (lds > 64 * 1024)
     HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&als_basis_kernel),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(als_basis_kernel, dim3(1), dim3(RED_NT), lds, s, AB, H64, Ht, HHt, table, F, k, 4, lam,
+  hipLaunchKernelGGL(als_basis_kernel, dim3(1), dim3(RED_NT), lds, s, AB, H64, Ht, HHt, table, F, k, KP, lam,
                      delta * delta, do_update);
   HIP_CHECK(hipGetLastError());
   return CNMF_OK;
@@ -6746,7 +6804,9 @@ int cnmf_als_sample_pass(const void* X, int x_dtype, void* W, const double* Ht, 
   hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
   int64_t als_rows = n_rows;
   int64_t row0 = 0, part0 = 0;
-  if (accumulate && use_sl(x_dtype, n_features, k)) {
+  // accumulate == CNMF_PASS_LOSS: no W-step; one ‖x − w·Hᵀ‖² partial per workgroup (fp64 Ht)
+  const bool loss = accumulate == CNMF_PASS_LOSS;
+  if (!loss && accumulate && use_sl(x_dtype, n_features, k)) {
     // the sample-lane ALS pass on the full tiles (its grid = the sl grid = the first partial rows),
     // the ragged tail (< 64 rows) on one workgroup of the VALU ALS pass (partial row g)
     int64_t n_full;
@@ -6770,18 +6830,19 @@ int cnmf_als_sample_pass(const void* X, int x_dtype, void* W, const double* Ht, 
   }
   PassKernel pk;
   const int np = (n_features + k + 63) / 64;
+  const int KP = padded_k(k);
   bool ok = false;
   switch (x_dtype) {
-    case CNMF_F32: ok = pick_als_tx<float>(n_features, np, &pk); break;
-    case CNMF_F64: ok = pick_als_tx<double>(n_features, np, &pk); break;
-    case CNMF_BF16: ok = pick_als_tx<bf16_t>(n_features, np, &pk); break;
+    case CNMF_F32: ok = pick_als_tx<float>(KP, n_features, np, &pk); break;
+    case CNMF_F64: ok = pick_als_tx<double>(KP, n_features, np, &pk); break;
+    case CNMF_BF16: ok = pick_als_tx<bf16_t>(KP, n_features, np, &pk); break;
   }
   if (!ok) return set_err(CNMF_ERR_UNSUPPORTED, "n_features=%d too wide for the ALS pass", n_features);
-  const size_t lds = pass_lds(n_features, 4, pk.sx, pk.sc, 8).total;
+  const size_t lds = pass_lds(n_features, KP, pk.sx, pk.sc, 8).total;
   if (lds > kMaxLds) return set_err(CNMF_ERR_UNSUPPORTED, "n_features=%d needs too much LDS", n_features);
   if (max_resident(pk.fn, lds) <= 0) return set_err(CNMF_ERR_HIP, "occupancy query failed");
   int F = n_features;
-  int flags = CNMF_PASS_UPDATE_W | (accumulate ? CNMF_PASS_ACCUMULATE : 0);
+  int flags = loss ? CNMF_PASS_LOSS : (CNMF_PASS_UPDATE_W | (accumulate ? CNMF_PASS_ACCUMULATE : 0));
   double d2 = sum_to_one * sum_to_one, zero = 0.0;
   const int64_t n_tiles = (als_rows + TS - 1) / TS;
   const void* Xr = static_cast<const unsigned char*>(X) + row0 * F * (int64_t)pk.sx;

@@ -771,8 +771,8 @@ class ALSPlan(MUPlan):
 
     def __init__(self, X: torch.Tensor, n_components: int, sum_to_one=0.0, smoothness=0.0, group=None):
         super().__init__(X, n_components, group=group)
-        if self.k > 4:
-            raise _lib.HipLibraryError(f"constrained ALS supports n_components <= 4 (got {self.k})")
+        if self.k > 8:
+            raise _lib.HipLibraryError(f"constrained ALS supports n_components <= 8 (got {self.k})")
         self.delta = float(sum_to_one or 0.0)
         self.lam = float(smoothness or 0.0)
         if self.delta < 0 or self.lam < 0:
@@ -801,6 +801,23 @@ class ALSPlan(MUPlan):
                 _ptr(self.partials), self.n_rows, self.F, self.k, self.delta, int(accumulate),
                 self._stream()), "cnmf_als_sample_pass")
 
+    def frobenius_error(self) -> float:
+        """As MUPlan.frobenius_error; above k = 4 through the ALS pass itself (its loss form reads the
+        fp64 Ht), k <= 4 as before."""
+        if self.k <= 4:
+            return super().frobenius_error()
+        if self.n_rows == 0:
+            self.loss_buf.zero_()
+        else:
+            with torch.cuda.device(self.device):
+                check(self.lib.cnmf_als_sample_pass(
+                    _ptr(self.X), self.xdt, _ptr(self.W), _ptr(self.Ht), _ptr(self.table),
+                    _ptr(self.partials), self.n_rows, self.F, self.k, self.delta, _lib.PASS_LOSS,
+                    self._stream()), "cnmf_als_sample_pass")
+            self.reduce(1, self.loss_buf)
+        self._allreduce(self.loss_buf)
+        return math.sqrt(max(float(self.loss_buf.item()), 0.0))
+
     def h_step(self):
         with torch.cuda.device(self.device):
             check(self.lib.cnmf_als_basis_update(
@@ -813,6 +830,9 @@ class ALSPlan(MUPlan):
                     "the W-step on the matrix cores (c = Hx and the 16 passive sets in fp64 MFMA), "
                     "in-launch reduction and H-step (one-wave BPP NNLS rows: Jacobi sweeps when "
                     "10*lambda <= B_jj/20, else block cyclic reduction; every workgroup)")
+        if self.k > 4:
+            return ("ALS W-step pass (mu_pass_kernel<KP=8, ALS>: block principal pivoting per sample on "
+                    "the Gram form, a quad per sample) + cnmf_reduce_partials + als_basis_kernel per iteration")
         return "ALS W-step pass + cnmf_reduce_partials + als_basis_kernel per iteration"
 
     def tune(self, *args, **kwargs) -> dict:

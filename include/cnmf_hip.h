@@ -230,9 +230,13 @@ int cnmf_normalise(void* W, int w_dtype, double* H64, double* Ht, double* HHt, d
                    int64_t n_rows, int n_features, int k, int norm, void* stream);
 
 /* ---- Constrained ALS (no sklearn counterpart — the spec and its
- * scipy-NNLS oracle are oracle/als_ref.py; DESIGN.md §Constrained ALS).  k <= 4, F <= 512.
- * table: cnmf_als_table_doubles() doubles = the W-step's passive-set inverses of
- * Q = HHᵀ + δ²11ᵀ (δ = sum_to_one), rebuilt by every basis call. */
+ * scipy-NNLS oracle are oracle/als_ref.py; DESIGN.md §Constrained ALS).  k <= 8; F <= 512 up to
+ * k = 4, above it what the H-step's LDS holds ((2k + 9)·8 + 12 + 16k bytes per feature in 160 KiB:
+ * F <= 480 at k = 8), else CNMF_ERR_UNSUPPORTED ("basis too large").  The persistent forms below
+ * serve k = 4 only.
+ * table: cnmf_als_table_doubles() doubles, rebuilt by every basis call: for k <= 4 the W-step's
+ * passive-set inverses of Q = HHᵀ + δ²11ᵀ (δ = sum_to_one); for k > 4 Q itself in the first 64
+ * doubles (stride 8, zero beyond k), the rest unused. */
 int cnmf_als_table_doubles(void);
 
 /* Ht / HHt / table from H64 (no update): before the first W-step. */
@@ -240,8 +244,12 @@ int cnmf_als_prepare(double* H64, double* Ht, double* HHt, double* table, int n_
                      double sum_to_one, void* stream);
 
 /* The W-step over all samples (one HBM pass): w_i = argmin_{w>=0} ‖x_i − Hᵀw‖² + δ²(1ᵀw − 1)²
- * exactly (passive-set enumeration on the Gram form), written to W; with accumulate, the
- * per-workgroup fp64 partials of [WᵀX | WᵀW] of the new W (rows: cnmf_pass_blocks). */
+ * exactly (k <= 4: passive-set enumeration on the Gram form; 5 <= k <= 8: block principal pivoting
+ * on the Gram form per sample, warm-started from the support of the W passed in), written to W; with accumulate, the
+ * per-workgroup fp64 partials of [WᵀX | WᵀW] of the new W (rows: cnmf_pass_blocks).
+ * accumulate = CNMF_PASS_LOSS (4): no W-step; W is read, and partials receives one double per
+ * workgroup row, the squared error ‖X − W·H‖² of its samples with the fp64 Ht (sum them with
+ * cnmf_reduce_partials(..., n_out = 1, ...)). */
 int cnmf_als_sample_pass(const void* X, int x_dtype, void* W, const double* Ht, const double* table,
                          double* partials, int64_t n_rows, int n_features, int k, double sum_to_one,
                          int accumulate, void* stream);
