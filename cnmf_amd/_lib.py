@@ -110,6 +110,13 @@ _SIGS = {
     "cnmf_mu_iterations_multi": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                         _i64, _i32, _i32, _f64, _f64, _f64, _f64, _vp, _i32, _vp, _i32,
                                         _vp]),
+    "cnmf_mb_rows": (_i64, [_i64]),
+    "cnmf_mb_row_doubles": (_i64, [_i32, _i32]),
+    "cnmf_mb_ctl_doubles": (_i64, [_i64]),
+    "cnmf_mb_step": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32,
+                            _f64, _f64, _f64, _f64, _i32, _vp]),
+    "cnmf_mb_solve_w": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _f64, _f64,
+                               _vp]),
 }
 
 

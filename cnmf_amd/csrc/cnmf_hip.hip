@@ -7838,4 +7838,5 @@ int cnmf_wmu_basis_update(const double* AD, double* H64, int n_features, int k, 
 #ifndef CNMF_SEPARATE
 #include "wt.hip"
 #include "init.hip"
+#include "minibatch.hip"
 #endif

@@ -375,6 +375,51 @@ int cnmf_host_register(void* ptr, int64_t bytes);
 int cnmf_host_unregister(void* ptr);
 int cnmf_copy_h2d_async(void* dst, const void* src, int64_t bytes, void* stream);
 
+/* ---- Minibatch (online) MU: scikit-learn 1.7.2's MiniBatchNMF (SKMB = class MiniBatchNMF of
+ * sklearn/decomposition/_nmf.py) with the stopping rules on the device (cnmf_amd/minibatch.py;
+ * DESIGN.md §3.9).  fp32 or fp64 X, W in X's type, 1 <= k <= 16, 1 <= n_features <= 512, any
+ * n_rows >= 1.  Every launch first reads ctl[CNMF_MB_STOPPED]: once it is set, the launch writes
+ * nothing, so a whole epoch of steps can be enqueued without a host round trip.
+ *
+ * cnmf_mb_step: ONE launch = SKMB _minibatch_step + _minibatch_convergence on the row window X, W
+ *   (n_rows = the batch's rows; l1 / l2: SKMB's per-batch regularisation):
+ *   with CNMF_MB_UPDATE_W  W <- W o (X Ht)/(W HHt + l1_W + l2_W W), zero denominator -> float32 eps;
+ *   batch cost = (0.5 ||X - W'H||^2 + l1_W sum W' + l1_H sum H + l2_W sum W'^2 + l2_H sum H^2) / n_rows
+ *   (old H); with CNMF_MB_UPDATE_H  Anum <- rho Anum + (W'^T X) o H, Bden <- rho Bden + (W'^T W') H
+ *   + l1_H + l2_H H (zero -> float32 eps), H <- Anum / Bden, Ht / HHt refreshed; the step count
+ *   advances; from the second step on SKMB's rules: stop when tol > 0 and ||H - H_old|| / ||H|| <= tol,
+ *   else the exponentially weighted cost (alpha = min(n_rows / (n_samples + 1), 1)) and stop after
+ *   max_no_improvement steps without a new minimum.
+ *   partials: cnmf_mb_rows(n_rows) rows of cnmf_mb_row_doubles(F, k) doubles (no memset needed);
+ *   counter: one zeroed uint32, left zero; Anum / Bden: k x F fp64 (start: H and 1).
+ * ctl: cnmf_mb_ctl_doubles(log_cap) doubles, zeroed by the caller, who then sets CNMF_MB_RHO,
+ *   CNMF_MB_TOL, CNMF_MB_MAX_NO_IMPROVE (negative = none), CNMF_MB_N_SAMPLES and CNMF_MB_LOG_CAP;
+ *   the launches maintain the rest: STOPPED, REASON (cnmf_mb_stop), STEPS_DONE, LAST_COST,
+ *   LAST_HDIFF, the EWA state, and from CNMF_MB_LOG up to log_cap entries (cost, H_diff, ewa), one
+ *   per step (NLOG counts them).
+ * cnmf_mb_solve_w: one iteration of SKMB _solve_W (H fixed: Ht / HHt) on the window, same gate;
+ *   partials: cnmf_mb_rows(n_rows) rows of 2 doubles; ctl[CNMF_MB_W_ITERS] counts the iterations
+ *   done, ctl[CNMF_MB_W_DIFF] = ||W' - W|| / ||W'||; tol > 0 and W_DIFF <= tol sets STOPPED.  Enqueue
+ *   max_iter launches and read the count once. */
+enum cnmf_mb_flags { CNMF_MB_UPDATE_W = 1, CNMF_MB_UPDATE_H = 2 };
+enum cnmf_mb_stop { CNMF_MB_STOP_NONE = 0, CNMF_MB_STOP_H_CHANGE = 1, CNMF_MB_STOP_NO_IMPROVEMENT = 2,
+                    CNMF_MB_STOP_W_CHANGE = 3 };
+enum cnmf_mb_slots {
+  CNMF_MB_STOPPED = 0, CNMF_MB_REASON = 1, CNMF_MB_STEPS_DONE = 2, CNMF_MB_LAST_COST = 3, CNMF_MB_LAST_HDIFF = 4,
+  CNMF_MB_EWA = 5, CNMF_MB_EWA_MIN = 6, CNMF_MB_NO_IMPROVE = 7, CNMF_MB_HAVE_EWA = 8, CNMF_MB_HAVE_MIN = 9,
+  CNMF_MB_RHO = 10, CNMF_MB_TOL = 11, CNMF_MB_MAX_NO_IMPROVE = 12, CNMF_MB_N_SAMPLES = 13, CNMF_MB_LOG_CAP = 14,
+  CNMF_MB_NLOG = 15, CNMF_MB_W_ITERS = 16, CNMF_MB_W_DIFF = 17, CNMF_MB_LOG = 32
+};
+int64_t cnmf_mb_rows(int64_t n_rows);
+int64_t cnmf_mb_row_doubles(int n_features, int k);
+int64_t cnmf_mb_ctl_doubles(int64_t log_cap);
+int cnmf_mb_step(const void* X, int x_dtype, void* W, double* H64, double* Ht, double* HHt, double* Anum,
+                 double* Bden, double* partials, int64_t n_parts, uint32_t* counter, double* ctl, int64_t n_rows,
+                 int n_features, int k, double l1_W, double l2_W, double l1_H, double l2_H, int flags, void* stream);
+int cnmf_mb_solve_w(const void* X, int x_dtype, void* W, const double* Ht, const double* HHt, double* partials,
+                    int64_t n_parts, uint32_t* counter, double* ctl, int64_t n_rows, int n_features, int k,
+                    double l1_W, double l2_W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
