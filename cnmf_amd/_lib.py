@@ -47,6 +47,7 @@ _SIGS = {
     "cnmf_last_error": (ctypes.c_char_p, []),
     "cnmf_padded_k": (_i32, [_i32]),
     "cnmf_pass_blocks": (_i64, [_i64, _i32, _i32, _i32]),
+    "cnmf_pass_describe": (_i32, [_i32, _i32, _i32, _i32, ctypes.c_char_p, _i32]),
     "cnmf_stage_doubles": (_i64, [_i32]),
     "cnmf_mu_sample_pass": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f64, _f64,
                                    _i32, _vp]),

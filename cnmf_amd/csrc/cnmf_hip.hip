@@ -4531,14 +4531,20 @@ __global__ __launch_bounds__(RED_NT) void reduce_kernel(const double* __restrict
   const int64_t hi = n_parts * (blockIdx.y + 1) / nslice;
   double s = 0.0;
   if (o < n_out) {
-    double v[RED_ROWS_PER_THREAD];
+    // one trip up to NSLICE·4·RED_ROWS_PER_THREAD = 2048 partial rows (every pass grid); more rows
+    // make longer slices
+    int64_t b0 = lo + r;
+    do {
+      double v[RED_ROWS_PER_THREAD];
 #pragma unroll
-    for (int u = 0; u < RED_ROWS_PER_THREAD; ++u) {
-      const int64_t b = lo + r + 4 * u;
-      v[u] = b < hi ? partials[b * n_out + o] : 0.0;
-    }
+      for (int u = 0; u < RED_ROWS_PER_THREAD; ++u) {
+        const int64_t b = b0 + 4 * u;
+        v[u] = b < hi ? partials[b * n_out + o] : 0.0;
+      }
 #pragma unroll
-    for (int u = 0; u < RED_ROWS_PER_THREAD; ++u) s += v[u];
+      for (int u = 0; u < RED_ROWS_PER_THREAD; ++u) s += v[u];
+      b0 += 4 * RED_ROWS_PER_THREAD;
+    } while (b0 < hi);
   }
   red[t] = s;
   __syncthreads();
@@ -4682,12 +4688,21 @@ struct PassKernel {
   int KP, NPW;
   bool split;
   size_t sx, sc;
+  // what was instantiated, for cnmf_pass_describe: the kernel template, TX and FT
+  const char* family = "";
+  const char* tx = "";
+  int FT = 0;
 };
+
+template <typename TX>
+constexpr const char* tx_name() {
+  return std::is_same<TX, float>::value ? "f32" : (std::is_same<TX, double>::value ? "f64" : "bf16");
+}
 
 template <typename TX, int KP, int FT, int NPW, bool SPLIT>
 static PassKernel make_pk() {
   return PassKernel{reinterpret_cast<PassFn>(&mu_pass_kernel<TX, KP, FT, NPW, SPLIT>), KP, NPW, SPLIT,
-                    sizeof(TX), sizeof(typename Compute<TX>::T)};
+                    sizeof(TX), sizeof(typename Compute<TX>::T), "mu_pass_kernel", tx_name<TX>(), FT};
 }
 
 template <typename TX, int KP, int FT, int NPW, bool SPLIT>
@@ -4738,7 +4753,7 @@ static bool pick_tx(int KP, int F, int np, PassKernel* out) {
 template <typename TX, int KP>
 static PassKernel make_mfma(int) {
   return PassKernel{reinterpret_cast<PassFn>(&mu_pass_mfma_kernel<TX, KP, 81>), KP, 0, true,
-                    sizeof(TX), sizeof(float)};
+                    sizeof(TX), sizeof(float), "mu_pass_mfma_kernel", tx_name<TX>(), 81};
 }
 
 // The matrix-core pass serves fp32 / bf16 X on the compile-time IOP grid (F = 81, V <= 97);
@@ -4799,7 +4814,8 @@ static int select_pass(int x_dtype, int F, int k, PassKernel* pk, size_t* lds, b
   if (F < 1 || k < 1) return set_err(CNMF_ERR_SHAPE, "invalid shape F=%d k=%d", F, k);
   if (k > 16) return set_err(CNMF_ERR_UNSUPPORTED, "k=%d > 16 is not supported", k);
   if (mfma_ok && !g_force_valu && use_bf16_mfma(x_dtype, F, k)) {
-    *pk = PassKernel{reinterpret_cast<PassFn>(&mu_pass_bf16_mfma_kernel), 16, 0, true, 2, 4};
+    *pk = PassKernel{reinterpret_cast<PassFn>(&mu_pass_bf16_mfma_kernel), 16, 0, true, 2, 4,
+                     "mu_pass_bf16_mfma_kernel", "bf16", 0};
     *lds = (size_t)bm::lds(F).total;
     return CNMF_OK;
   }
@@ -6523,7 +6539,7 @@ static constexpr int64_t kWmuMaxBlocks = 512;  // two per CU resident (occupancy
 
 extern "C" {
 
-int cnmf_abi_version(void) { return 302; }
+int cnmf_abi_version(void) { return 303; }
 
 const char* cnmf_last_error(void) { return g_err; }
 
@@ -6588,15 +6604,79 @@ static int launch_tail(const PassKernel& pk, size_t lds, const void* X, void* W,
   return CNMF_OK;
 }
 
+static int check_pass_flags(int flags) {
+  const int valid = CNMF_PASS_UPDATE_W | CNMF_PASS_ACCUMULATE | CNMF_PASS_LOSS;
+  if ((flags & ~valid) || flags == 0 || ((flags & CNMF_PASS_LOSS) && flags != CNMF_PASS_LOSS) ||
+      ((flags & CNMF_PASS_ACCUMULATE) && !(flags & CNMF_PASS_UPDATE_W)))
+    return set_err(CNMF_ERR_ARG, "invalid flags %d", flags);
+  return CNMF_OK;
+}
+
+// The kernels one cnmf_mu_sample_pass call launches (host only: cnmf_pass_describe prints the same
+// answer).  PASS_GRID: *pk over every tile.  PASS_SL / PASS_BFW: the sample-lane / wave-tile bf16
+// kernel over the full 64-sample tiles, and *pk on one workgroup for a ragged tail.  The loss pass
+// and the sample-lane shape's other passes take the VALU kernel.
+enum PassPath { PASS_GRID, PASS_SL, PASS_BFW };
+static int route_pass(int x_dtype, int F, int k, int flags, bool have_partials, const PassKernel& pmain,
+                      size_t lmain, PassPath* path, PassKernel* pk, size_t* lds) {
+  const bool sl_path = use_sl(x_dtype, F, k);
+  *pk = pmain;
+  *lds = lmain;
+  if (sl_path && flags == (CNMF_PASS_UPDATE_W | CNMF_PASS_ACCUMULATE)) {
+    *path = PASS_SL;
+    return select_pass(x_dtype, F, k, pk, lds, false);  // the VALU pass
+  }
+  if (use_bfw(x_dtype, F, k) && (flags & CNMF_PASS_UPDATE_W) && have_partials) {
+    *path = PASS_BFW;  // its tail: the 64-sample matrix-core pass
+    return CNMF_OK;
+  }
+  *path = PASS_GRID;
+  if ((flags & CNMF_PASS_LOSS) || sl_path) return select_pass(x_dtype, F, k, pk, lds, false);
+  return CNMF_OK;
+}
+
+static bool bfw_is_cfg4(int F, int k) {
+  return bfw_fn(F, k) == reinterpret_cast<PassFn>(&mu_pass_bfw_kernel<10, 16>);
+}
+
+// "<kernel with its template arguments> lds=<dynamic LDS bytes>"
+static int describe_pk(const PassKernel& pk, size_t lds, char* out, size_t len) {
+  if (!strcmp(pk.family, "mu_pass_kernel"))
+    return snprintf(out, len, "mu_pass_kernel<TX=%s, KP=%d, FT=%d, NPW=%d, SPLIT=%d> lds=%zu", pk.tx, pk.KP, pk.FT,
+                    pk.NPW, (int)pk.split, lds);
+  if (!strcmp(pk.family, "mu_pass_mfma_kernel"))
+    return snprintf(out, len, "mu_pass_mfma_kernel<TX=%s, KP=%d, FT=%d> lds=%zu", pk.tx, pk.KP, pk.FT, lds);
+  return snprintf(out, len, "%s lds=%zu", pk.family, lds);
+}
+
+int cnmf_pass_describe(int n_features, int k, int x_dtype, int flags, char* out, int len) {
+  if (!out || len < 1) return set_err(CNMF_ERR_ARG, "null pointer argument");
+  if (int st = check_pass_flags(flags)) return st;
+  PassKernel pmain, pk;
+  size_t lmain = 0, lds = 0;
+  int st = select_pass(x_dtype, n_features, k, &pmain, &lmain);
+  if (st) return st;
+  PassPath path;
+  st = route_pass(x_dtype, n_features, k, flags, true, pmain, lmain, &path, &pk, &lds);
+  if (st) return st;
+  char one[160];
+  describe_pk(pk, lds, one, sizeof one);
+  if (path == PASS_SL)
+    snprintf(out, (size_t)len, "mu_pass_sl_kernel lds=%zu; ragged tail: %s", (size_t)sl::L_TOTAL, one);
+  else if (path == PASS_BFW)
+    snprintf(out, (size_t)len, "mu_pass_bfw_kernel<%s> lds=%zu; ragged tail: %s",
+             bfw_is_cfg4(n_features, k) ? "10, 16" : "0, 0", (size_t)bw::lds(n_features).total, one);
+  else
+    snprintf(out, (size_t)len, "%s", one);
+  return CNMF_OK;
+}
+
 int cnmf_mu_sample_pass(const void* X, int x_dtype, void* W, const double* Ht, const double* HHt,
                         double* partials, int64_t n_rows, int n_features, int k, double l1_W,
                         double l2_W, int flags, void* stream) {
   if (n_rows < 0) return set_err(CNMF_ERR_SHAPE, "n_rows < 0");
   if (!X || !W || !Ht || !HHt) return set_err(CNMF_ERR_ARG, "null pointer argument");
-  const int valid = CNMF_PASS_UPDATE_W | CNMF_PASS_ACCUMULATE | CNMF_PASS_LOSS;
-  if ((flags & ~valid) || flags == 0 || ((flags & CNMF_PASS_LOSS) && flags != CNMF_PASS_LOSS) ||
-      ((flags & CNMF_PASS_ACCUMULATE) && !(flags & CNMF_PASS_UPDATE_W)))
-    return set_err(CNMF_ERR_ARG, "invalid flags %d", flags);
+  if (int st = check_pass_flags(flags)) return st;
   if ((flags & (CNMF_PASS_ACCUMULATE | CNMF_PASS_LOSS)) && !partials)
     return set_err(CNMF_ERR_ARG, "partials required");
   if (int st = check_xw_aligned(X, W)) return st;
@@ -6611,8 +6691,12 @@ int cnmf_mu_sample_pass(const void* X, int x_dtype, void* W, const double* Ht, c
   if (nb == 0) return CNMF_OK;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   int F = n_features;
-  const bool sl_path = use_sl(x_dtype, n_features, k);
-  if (sl_path && flags == (CNMF_PASS_UPDATE_W | CNMF_PASS_ACCUMULATE)) {
+  PassPath path;
+  PassKernel pk;
+  size_t lds = 0;
+  st = route_pass(x_dtype, n_features, k, flags, partials != nullptr, pmain, lmain, &path, &pk, &lds);
+  if (st) return st;
+  if (path == PASS_SL) {
     int64_t n_full;
     bool tail;
     const int64_t g = sl_grid(n_rows, &n_full, &tail);
@@ -6623,13 +6707,9 @@ int cnmf_mu_sample_pass(const void* X, int x_dtype, void* W, const double* Ht, c
       HIP_CHECK(hipGetLastError());
     }
     if (!tail) return CNMF_OK;
-    PassKernel pk;  // the VALU pass
-    size_t lds = 0;
-    st = select_pass(x_dtype, n_features, k, &pk, &lds, false);
-    if (st) return st;
     return launch_tail(pk, lds, X, W, Ht, HHt, partials, n_rows, n_full, g, F, k, l1_W, l2_W, flags, s);
   }
-  if (use_bfw(x_dtype, n_features, k) && (flags & CNMF_PASS_UPDATE_W) && partials) {
+  if (path == PASS_BFW) {
     const int64_t n_full = n_rows / TS;
     int64_t g = 0;
     if (n_full > 0) {
@@ -6641,16 +6721,10 @@ int cnmf_mu_sample_pass(const void* X, int x_dtype, void* W, const double* Ht, c
       HIP_CHECK(hipLaunchKernel(bfw_fn(F, k), dim3((unsigned)g), dim3(NT), args, lb, s));
     }
     if (n_rows % TS == 0) return CNMF_OK;
-    // the 64-sample matrix-core pass
-    return launch_tail(pmain, lmain, X, W, Ht, HHt, partials, n_rows, n_full, g, F, k, l1_W, l2_W, flags, s);
+    return launch_tail(pk, lds, X, W, Ht, HHt, partials, n_rows, n_full, g, F, k, l1_W, l2_W, flags, s);
   }
-  PassKernel pk = pmain;
-  size_t lds = lmain;
-  if ((flags & CNMF_PASS_LOSS) || sl_path) {
-    st = select_pass(x_dtype, n_features, k, &pk, &lds, false);
-    if (st) return st;
-    if (max_resident(pk.fn, lds) <= 0) return set_err(CNMF_ERR_HIP, "occupancy query failed");
-  }
+  // (cached after the first call; it also raises the kernel's LDS ceiling when lds > 64 KiB)
+  if (max_resident(pk.fn, lds) <= 0) return set_err(CNMF_ERR_HIP, "occupancy query failed");
   const int64_t n_tiles = (n_rows + TS - 1) / TS;
   void* args[] = {(void*)&X, &W, (void*)&Ht, (void*)&HHt, &partials, &n_rows, &F, &k, &l1_W, &l2_W, &flags, (void*)&n_tiles};
   HIP_CHECK(hipLaunchKernel(pk.fn, dim3((unsigned)nb), dim3(NT), args, lds, s));
@@ -6676,8 +6750,6 @@ static int launch_reduce(const double* partials, int64_t n_parts, int n_out, dou
     HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&reduce_kernel),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int nslice = (int)std::max<int64_t>(1, std::min<int64_t>(NSLICE, (n_parts + 4 * RED_ROWS_PER_THREAD - 1) / (4 * RED_ROWS_PER_THREAD)));
-  if ((int64_t)nslice * 4 * RED_ROWS_PER_THREAD < n_parts)
-    return set_err(CNMF_ERR_UNSUPPORTED, "too many partial rows (%lld) for one reduction", (long long)n_parts);
   if ((n_out + 63) / 64 > RED_MAX_COLS) return set_err(CNMF_ERR_UNSUPPORTED, "n_out=%d too wide for the reduction", n_out);
   dim3 grid((unsigned)((n_out + 63) / 64), (unsigned)nslice);
   hipLaunchKernelGGL(reduce_kernel, grid, dim3(RED_NT), lds, s, partials, n_parts, n_out, nslice,

@@ -62,6 +62,16 @@ int cnmf_padded_k(int k);
  * Negative on error (e.g. unsupported shape or no device). */
 int64_t cnmf_pass_blocks(int64_t n_rows, int n_features, int k, int x_dtype);
 
+/* The kernels cnmf_mu_sample_pass(flags, with a partials buffer) launches for this shape, as text
+ * into out[len]; host only (no HIP call, no device needed).  Each kernel reads
+ *   mu_pass_kernel<TX=f32|f64|bf16, KP=.., FT=.., NPW=.., SPLIT=0|1> lds=<dynamic LDS bytes>
+ *   mu_pass_mfma_kernel<TX=.., KP=.., FT=81> lds=..      mu_pass_bf16_mfma_kernel lds=..
+ * and the two families that serve full 64-sample tiles only add the kernel of a ragged tail:
+ *   mu_pass_sl_kernel lds=..; ragged tail: <kernel>      mu_pass_bfw_kernel<..> lds=..; ragged tail: <kernel>
+ * Returns 0, or the status cnmf_mu_sample_pass would give for the shape (CNMF_ERR_UNSUPPORTED for
+ * k > 16 or a row too wide for the LDS tile, CNMF_ERR_SHAPE, CNMF_ERR_ARG). */
+int cnmf_pass_describe(int n_features, int k, int x_dtype, int flags, char* out, int len);
+
 /* Doubles needed by the cross-block reduction stage buffer for n_out outputs. */
 int64_t cnmf_stage_doubles(int n_out);
 

@@ -3,7 +3,8 @@
 Wide rows (n_out >= 1024, <= 1024 partial rows) take the one-level reduce_wide_kernel since round 6
 (cfg4's [WᵀX | WᵀW] rows, the init Gram rows); narrower or taller inputs keep the two-level
 reduce_kernel.  Both sum in a fixed order: two runs are bit-identical.  Bar: 1e-13 relative to the
-column's absolute sum (fp64 rounding of <= 1024 terms).
+column's absolute sum (fp64 rounding of <= 1024 terms; the two-level kernel's 2049 rows pass through
+sums of at most 17 + 4 + 16 + 4 terms, far inside it).
 """
 import numpy as np
 import pytest
@@ -12,7 +13,10 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("n_parts,n_out", [(0, 5056), (1, 5056), (7, 1024), (256, 5056), (257, 6642),
-                                           (1024, 2000), (1100, 5056), (256, 340)])
+                                           (1024, 2000), (1100, 5056), (256, 340)]
+                         # narrow outputs (the loss: n_out = 1) around the 64-column block, at one
+                         # row, one row past the first slice of 32, one past 64 slices of 32
+                         + [(p, o) for p in (1, 33, 2049) for o in (1, 2, 63, 64, 65)])
 def test_reduce_partials_matches_numpy(n_parts, n_out):
     import torch
     from cnmf_amd._lib import check, load

@@ -112,7 +112,7 @@ def test_library_exports_the_minibatch_symbols():
     declared = _lib.declared_symbols()
     for s in NEW_SYMBOLS:
         assert s in declared and s in _lib._SIGS and hasattr(lib, s), s
-    assert lib.cnmf_abi_version() == 302
+    assert lib.cnmf_abi_version() == 303
 
 
 def test_sizing_helpers_answer_without_a_gpu():
