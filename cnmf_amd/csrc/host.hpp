@@ -39,6 +39,7 @@ struct WtLaunch {
   bool mf;       // k = 8 on the matrix cores (mu_iter_mf8_kernel)
   int nres = 0;  // W streamed: the first nres tiles of every wave resident in the LDS left over
   bool wres = false;  // W resident (every tile)
+  int x_keep16 = 0;   // sixteenths of X kept in the Infinity Cache across iterations (csrc/keep.hpp)
 };
 CNMF_LOCAL int wt_pd(int k, bool wres, bool multi);
 CNMF_LOCAL bool wt_plan(int64_t n_rows, int x_dtype, int F, int k, bool multi, int layout, WtLaunch* out,

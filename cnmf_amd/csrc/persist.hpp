@@ -61,6 +61,10 @@ struct PersistArgs {
   // on, and only when the XCC table shows every member of the group on the combiner's XCC (placement
   // is never assumed: a group spread over XCDs keeps the write-through stores)
   int l2rows = 0;
+  // mu_iter_wt_kernel: sixteenths of X loaded with the default cache policy, so that they stay in the
+  // Infinity Cache from one iteration to the next; the rest streams through `nt` (0 = every load `nt`;
+  // csrc/keep.hpp chooses it)
+  int x_keep16 = 0;
 };
 
 // the arguments of a persistent launch of G workgroups (n_static = 0, l2rows = 0: the callers' own)

@@ -2,6 +2,7 @@
 // (cfg2, cfg3), with wt_plan and launch_wt.
 #include "wt.hpp"
 #include "host.hpp"
+#include "keep.hpp"
 
 namespace cnmf {
 
@@ -81,6 +82,7 @@ __global__ __launch_bounds__(NT, 1) void mu_iter_wt_kernel(PersistArgs a) {
   // 5): their W loads re-load an X chunk (the counted waits see the same loads) and their stores go
   // to the dummy word (the same stores), the rest streams
   const int nres = WRES ? 0 : __builtin_amdgcn_readfirstlane(a.n_static);
+  const int xkeep = __builtin_amdgcn_readfirstlane(a.x_keep16);  // sixteenths of X kept in the cache
   float* wres = reinterpret_cast<float*>(smem + G_::L_WRES + (size_t)w * (WRES ? nbt_max : nres) * WBW);  // [i][TSW][K]
   float* red = reinterpret_cast<float*>(smem + G_::L_RED);
   double* sH = reinterpret_cast<double*>(smem + G_::L_H);
@@ -181,9 +183,10 @@ __global__ __launch_bounds__(NT, 1) void mu_iter_wt_kernel(PersistArgs a) {
 #else
     const unsigned char* xs = Xb + (size_t)tile * XBW + 16 * l;
 #endif
-#pragma unroll
-    for (int u = 0; u < PFW - 1; ++u) ld16(pf[u], xs + 1024 * u);
-    ld16(pf[PFW - 1], l < LASTL ? xs + 1024 * (PFW - 1) : xs);
+    // X kept in the Infinity Cache: tile position ti of this wave loads with the
+    // default policy when ((ti + gw) & 15) < x_keep16 — the same addresses in every iteration, the
+    // same share in every wave, the HBM-served positions spread over the chip at every moment
+    ld_set<PFW>(pf, xs, l < LASTL ? xs + 1024 * (PFW - 1) : xs, (ti + gw) & 15, xkeep);
     if (!WRES) ld16(pf[PFW], (l < WBW / 16 && ti >= nres) ? Wb + (size_t)tile * WBW + 16 * l : xs);
   };
   auto stage = [&](const u32x4 (&pf)[PFS]) {
@@ -743,7 +746,16 @@ bool wt_plan(int64_t n_rows, int x_dtype, int F, int k, bool multi, int layout, 
     }
     const PassFn fn = mf ? mf8_fn(wres != 0, multi, tol) : wt_fn(k, wres != 0, multi, tol);
     if (max_resident(fn, lds) < G) continue;  // the whole grid co-resident (cached query)
-    *out = WtLaunch{fn, G, n_tiles, lds, mf, nres, wres != 0};
+    // the share of X kept in the Infinity Cache (the VALU wave tiles): W streams for the tiles past
+    // every wave's nres resident ones, read and written once per iteration.  CNMF_WT_KEEP16
+    // (diagnostic) overrides the rule.
+    int keep16 = 0;
+    if (!mf) {
+      const int64_t w_tiles = wres ? 0 : std::max<int64_t>(0, n_tiles - (int64_t)nres * wt::NWV * G);
+      keep16 = wt_keep16(n_rows * (int64_t)wt::F * 4, 2 * w_tiles * wbw);
+      if (const char* kp = diag_env("CNMF_WT_KEEP16")) keep16 = std::min(16, std::max(0, atoi(kp)));
+    }
+    *out = WtLaunch{fn, G, n_tiles, lds, mf, nres, wres != 0, keep16};
     return true;
   }
   return false;
@@ -765,6 +777,7 @@ int launch_wt(const WtLaunch& L, int n_iter, const void* X, void* W, double* H64
     if (atoi(gz) > 0) pa.n_groups = (int)std::min<int64_t>((L.G + atoi(gz) - 1) / atoi(gz), sl::MAX_GROUPS);
   pa.n_static = L.nres;
   pa.l2rows = L.mf ? 0 : wt_l2rows();
+  pa.x_keep16 = L.x_keep16;
   void* args[] = {&pa};
   HIP_CHECK(hipLaunchKernel(L.fn, dim3((unsigned)L.G), dim3(NT), args, L.lds, s));
   return CNMF_OK;

@@ -138,6 +138,54 @@ __device__ __forceinline__ float sum_over_row16(float v) {
 __device__ __forceinline__ void ld16(u32x4& r, const unsigned char* p) {
   asm volatile(WT_LD : "=a"(r) : "v"(p) : "memory");
 }
+// The X loads of one prefetch set (mu_iter_wt_kernel): chunks p + 1024·u (u < C - 1) and plast, with
+// the default cache policy when pos < keep (the tile belongs to the share of X kept in the Infinity
+// Cache across iterations, PersistArgs::x_keep16), else WT_LD's `nt`.  ONE asm statement holding
+// both forms behind a scalar branch: the two forms write the same AGPR tuples, so the compiler sees
+// one definition per tuple and has nothing to merge with copies (a copy behind a load that has not
+// landed is the stale-tile failure the counted waits exist to prevent).  Either path issues the same
+// C loads in the same order; pos and keep are wave-uniform.  The 13-bit offset field ends at 4095:
+// the chunk at 4096 takes its own address.
+#ifdef CNMF_X_PLAIN
+#define WT_LD_ST(d, a, o) "global_load_dwordx4 " d ", " a ", off offset:" o "\n\t"
+#else
+#define WT_LD_ST(d, a, o) "global_load_dwordx4 " d ", " a ", off offset:" o " nt\n\t"
+#endif
+#define WT_LD_KP(d, a, o) "global_load_dwordx4 " d ", " a ", off offset:" o "\n\t"
+template <int C>
+__device__ __forceinline__ void ld_set(u32x4* pf, const unsigned char* p, const unsigned char* plast, int pos,
+                                       int keep) {
+  if constexpr (C == 6) {
+    const unsigned char* p4 = p + 4096;
+    asm volatile(
+        "s_cmp_lt_u32 %[pos], %[keep]\n\t"
+        "s_cbranch_scc0 .Lwt_st%=\n\t"
+        WT_LD_KP("%0", "%[p]", "0") WT_LD_KP("%1", "%[p]", "1024") WT_LD_KP("%2", "%[p]", "2048")
+        WT_LD_KP("%3", "%[p]", "3072") WT_LD_KP("%4", "%[p4]", "0") WT_LD_KP("%5", "%[pl]", "0")
+        "s_branch .Lwt_end%=\n"
+        ".Lwt_st%=:\n\t"
+        WT_LD_ST("%0", "%[p]", "0") WT_LD_ST("%1", "%[p]", "1024") WT_LD_ST("%2", "%[p]", "2048")
+        WT_LD_ST("%3", "%[p]", "3072") WT_LD_ST("%4", "%[p4]", "0") WT_LD_ST("%5", "%[pl]", "0")
+        "\n.Lwt_end%=:"
+        : "=&a"(pf[0]), "=&a"(pf[1]), "=&a"(pf[2]), "=&a"(pf[3]), "=&a"(pf[4]), "=&a"(pf[5])
+        : [p] "v"(p), [p4] "v"(p4), [pl] "v"(plast), [pos] "s"(pos), [keep] "s"(keep)
+        : "memory", "scc");
+  } else if constexpr (C == 3) {
+    asm volatile(
+        "s_cmp_lt_u32 %[pos], %[keep]\n\t"
+        "s_cbranch_scc0 .Lwt_st%=\n\t"
+        WT_LD_KP("%0", "%[p]", "0") WT_LD_KP("%1", "%[p]", "1024") WT_LD_KP("%2", "%[pl]", "0")
+        "s_branch .Lwt_end%=\n"
+        ".Lwt_st%=:\n\t"
+        WT_LD_ST("%0", "%[p]", "0") WT_LD_ST("%1", "%[p]", "1024") WT_LD_ST("%2", "%[pl]", "0")
+        "\n.Lwt_end%=:"
+        : "=&a"(pf[0]), "=&a"(pf[1]), "=&a"(pf[2])
+        : [p] "v"(p), [pl] "v"(plast), [pos] "s"(pos), [keep] "s"(keep)
+        : "memory", "scc");
+  } else {
+    static_assert(C == 3 || C == 6, "X loads per prefetch set");
+  }
+}
 template <int N>
 __device__ __forceinline__ void wait_n() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
