@@ -118,6 +118,12 @@ _SIGS = {
                             _f64, _f64, _f64, _f64, _i32, _vp]),
     "cnmf_mb_solve_w": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _f64, _f64,
                                _vp]),
+    "cnmf_hals_rows": (_i64, [_i64]),
+    "cnmf_hals_row_doubles": (_i64, [_i32, _i32]),
+    "cnmf_hals_ctl_doubles": (_i64, [_i64]),
+    "cnmf_hals_step": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32,
+                              _f64, _f64, _f64, _f64, _i32, _vp]),
+    "cnmf_hals_loss": (_i32, [_vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp]),
 }
 
 

@@ -9,7 +9,9 @@ scikit-learn 1.7.2's Frobenius MU path (SK = sklearn/decomposition/_nmf.py):
   _initialize_nmf ('random')    SK:303-314   (nndsvd / nndsvda / nndsvdar: cnmf_amd.init)
 
 Differences, all deliberate: the solvers are 'mu' (the default here; sklearn's default 'cd'
-raises) and the build's constrained ALS 'als' (sum_to_one / smoothness; k ≤ 8),
+raises), the build's constrained ALS 'als' (sum_to_one / smoothness; k ≤ 8) and
+'hals' — sklearn's 'cd' algorithm itself (`_fit_coordinate_descent`, SK:376-523, shuffle=False:
+the Fast HALS sweep and its stopping rule; fp32 / fp64 X on one device; the name 'cd' stays refused),
 only beta_loss='frobenius' is accepted, sparse X is not, and n_components ≤ 16.  normalise=
 ('l1' | 'l2' | 'max') adds the §8 a6 projection (off by default, so 'mu' output is sklearn's).  NumPy
 inputs are copied to the GPU and results come back as NumPy arrays of X's dtype; torch tensors on a
@@ -121,9 +123,10 @@ def _validate_params(n_components, init, solver, beta_loss, tol, max_iter, alpha
     if init not in _INITS:
         raise ValueError(f"The 'init' parameter must be a str among {{'custom', 'nndsvd', "
                          f"'nndsvda', 'nndsvdar', 'random'}} or None. Got {init!r} instead.")
-    if solver not in ("mu", "als"):
+    if solver not in ("mu", "als", "hals"):
         raise ValueError(f"solver={solver!r} is not available: this build implements the "
-                         "multiplicative-update solver ('mu') and the constrained ALS ('als').")
+                         "multiplicative-update solver ('mu') and the constrained ALS ('als'), "
+                         "and HALS ('hals').")
     if beta_loss not in ("frobenius", 2, 2.0):
         raise ValueError(f"beta_loss={beta_loss!r} is not available: only 'frobenius' (2) is "
                          "implemented on the MI355X path.")
@@ -185,6 +188,17 @@ def _validate_weights(weights, X, solver, alpha_W, alpha_H, normalise):
     if (_is_torch(X) and X.dtype != torch.float32) or (not _is_torch(X) and X.dtype != np.float32):
         raise TypeError("the weighted MU runs in float32: pass X (and W, H) as float32")
     return Mw
+
+
+def _validate_hals(solver, shuffle, devices=None):
+    """solver='hals' (sklearn's 'cd' sweep, SK:376-523) runs the cyclic order on one device."""
+    if solver != "hals":
+        return
+    if shuffle:
+        raise ValueError("shuffle=True is not available for solver='hals': the sweep visits the "
+                         "components in cyclic order (sklearn's shuffle=False).")
+    if devices is not None:
+        raise ValueError("devices= is not available for solver='hals': it runs on one device.")
 
 
 _TORCH_DT = {}  # numpy scalar type -> torch dtype, filled on first use
@@ -260,6 +274,8 @@ def _resolve(X, W, H, n_components, init, update_H, alpha_W, alpha_H, l1_ratio, 
     X = _check_X(X)
     Mw = _validate_weights(weights, X, solver, alpha_W, alpha_H, normalise)
     as_torch = _is_torch(X)
+    if solver == "hals" and as_torch and X.dtype == torch.bfloat16:
+        raise TypeError("bfloat16 X is not available for solver='hals': pass float32 or float64")
     streamed = _streamed(X, as_torch, memory_budget, solver, Mw)
     n_samples, n_features = X.shape
     k = n_components
@@ -289,7 +305,7 @@ def _resolve(X, W, H, n_components, init, update_H, alpha_W, alpha_H, l1_ratio, 
             k = H.shape[0]
         if H.dtype != X.dtype and not (as_torch and X.dtype == torch.bfloat16):
             raise TypeError("H should have the same dtype as X. Got H.dtype = {}.".format(_dtype_name(H)))
-        W = None  # filled with sqrt(X.mean()/k) below (SK:1228-1232)
+        W = None  # filled with sqrt(X.mean()/k), for 'hals' with zeros, below (SK:1228-1235)
     else:
         if W is not None or H is not None:
             warnings.warn("When init!='custom', provided W or H are ignored. Set  init='custom' to "
@@ -313,7 +329,7 @@ def _make_plan(X, Mw, k, regs, dev, *, solver="mu", sum_to_one=None, smoothness=
                streamed=False, memory_budget=None):
     """The plan (device state + launches) that runs the fit of X (all of it, or one shard)."""
     torch = _torch()
-    from .solver import ALSPlan, MUPlan, WeightedMUPlan
+    from .solver import ALSPlan, HALSPlan, MUPlan, WeightedMUPlan
     if streamed:  # §8 f3: X stays in host memory and streams through a memory_budget of HBM
         from .outofcore import StreamedMUPlan
         return StreamedMUPlan(X, k, regs[0], regs[2], regs[1], regs[3], group=group, device=dev,
@@ -325,6 +341,8 @@ def _make_plan(X, Mw, k, regs, dev, *, solver="mu", sum_to_one=None, smoothness=
         return WeightedMUPlan(Xd, Md, k, group=group)
     if solver == "als":
         return ALSPlan(Xd, k, sum_to_one=sum_to_one, smoothness=smoothness, group=group)
+    if solver == "hals":
+        return HALSPlan(Xd, k, regs[0], regs[2], regs[1], regs[3], group=group)
     return MUPlan(Xd, k, regs[0], regs[2], regs[1], regs[3], group=group)
 
 
@@ -351,7 +369,7 @@ def _fit_transform(X, W, H, n_components, init, update_H, tol, max_iter, alpha_W
                    memory_budget=None, init_device="auto"):
     """`_BaseNMF._fit_transform` for solver='mu' (SK:1638-1734) on the MI355X path."""
     torch = _torch()
-    from .solver import run_mu
+    from .solver import run_hals, run_mu
 
     X, Mw, as_torch, streamed, k, W, H, regs = _resolve(
         X, W, H, n_components, init, update_H, alpha_W, alpha_H, l1_ratio, random_state, device,
@@ -361,9 +379,13 @@ def _fit_transform(X, W, H, n_components, init, update_H, tol, max_iter, alpha_W
         X.device if as_torch and X.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device()))
     plan = _make_plan(X, Mw, k, regs, dev, solver=solver, sum_to_one=sum_to_one, smoothness=smoothness,
                       group=group, streamed=streamed, memory_budget=memory_budget)
-    _start(plan, W, H, _transform_start(X, as_torch, k) if W is None else None)
+    avg = None
+    if W is None:  # the update_H=False start; sklearn's non-'mu' branch is zeros (SK:1233-1235)
+        avg = 0.0 if solver == "hals" else _transform_start(X, as_torch, k)
+    _start(plan, W, H, avg)
     try:
-        n_iter = run_mu(plan, max_iter=max_iter, tol=tol, update_H=update_H, verbose=verbose)
+        run = run_hals if solver == "hals" else run_mu
+        n_iter = run(plan, max_iter=max_iter, tol=tol, update_H=update_H, verbose=verbose)
         if n_iter == max_iter and tol > 0:
             warnings.warn("Maximum number of iterations %d reached. Increase it to improve "
                           "convergence." % max_iter, ConvergenceWarning)
@@ -412,6 +434,12 @@ def factorise(X, W=None, H=None, n_components="auto", *, init=None, update_H=Tru
     non-negative least squares with a sum-to-one penalty of weight `sum_to_one` (δ; None = off),
     and per basis row the exact NNLS with a second-difference smoothness penalty `smoothness` (λ)
     — see oracle/als_ref.py for the precise objective.  tol / max_iter work as for 'mu'.
+    solver='hals' is sklearn's solver='cd' with shuffle=False (SK:376-523): per iteration one
+    Gauss-Seidel sweep of every row of W and then of every column of H, alpha_W / alpha_H /
+    l1_ratio honoured, and sklearn's rule: stop when the projected-gradient violation has fallen
+    to tol times its first value (tested every iteration).  One launch per iteration, the rule on
+    the device.  float32 / float64 X on one device; no weights, memory_budget streaming, devices=
+    or shuffle=True.  The update_H=False start is W = 0, as sklearn's.
     `weights` (array of X's shape, >= 0; None = off) selects the weighted / masked MU (SURVEY.md
     §8(f) row 2, oracle/wmu_ref.py): the loss becomes Σ m·(x − wh)², so a weight 0 marks a missing
     value (give X any finite non-negative entry there) and 1/σ² an uncertainty weight; float32 X,
@@ -430,6 +458,7 @@ def factorise(X, W=None, H=None, n_components="auto", *, init=None, update_H=Tru
     _validate_params(n_components, init, solver, beta_loss, tol, max_iter, alpha_W, alpha_H, l1_ratio)
     _validate_normalise(normalise)
     _validate_als(solver, alpha_W, alpha_H, sum_to_one, smoothness)
+    _validate_hals(solver, shuffle, devices)
     _validate_init_device(init_device)
     if devices is not None:
         from .multidevice import factorise_devices
@@ -501,6 +530,7 @@ class NMF:
                          self.max_iter, self.alpha_W, self.alpha_H, self.l1_ratio)
         _validate_normalise(self.normalise)
         _validate_als(self.solver, self.alpha_W, self.alpha_H, self.sum_to_one, self.smoothness)
+        _validate_hals(self.solver, self.shuffle)
         _validate_init_device(self.init_device)
 
     def fit_transform(self, X, y=None, W=None, H=None, weights=None):

@@ -7911,4 +7911,5 @@ int cnmf_wmu_basis_update(const double* AD, double* H64, int n_features, int k, 
 #include "wt.hip"
 #include "init.hip"
 #include "minibatch.hip"
+#include "hals.hip"
 #endif

@@ -760,6 +760,147 @@ def run_mu(plan: MUPlan, max_iter: int = 200, tol: float = 1e-4, update_H: bool 
     return it
 
 
+# solver='hals': control-block slots and flags (include/cnmf_hip.h: cnmf_hals_slots, cnmf_hals_flags)
+(HALS_STOPPED, HALS_ITERS_DONE, HALS_VIOL_INIT, HALS_VIOL_LAST, HALS_TOL, HALS_LOG_CAP, HALS_NLOG) = range(7)
+HALS_LOG = 16
+HALS_UPDATE_H = 1
+HALS_STRETCH = 16  # launches enqueued between two reads of the control block
+
+
+class HALSPlan(MUPlan):
+    """Device state of solver='hals': sklearn's coordinate-descent solver with shuffle=False (SKCD =
+    `_fit_coordinate_descent`, SK:376-523).  One iteration — the W-sweep, the H-sweep and the
+    stopping rule — is ONE launch (cnmf_hals_step, csrc/hals.hip); a stop sets a word on the device
+    that turns every later launch into a no-op.  MUPlan's X / W / H64 / Ht / HHt state, set_W, set_H,
+    refresh_basis and normalise are reused; the partial rows, the ticket word, the control block
+    and the loss launch behind frobenius_error (cnmf_hals_loss) are the plan's own.  fp32 / fp64
+    X, one device."""
+
+    def __init__(self, X: torch.Tensor, n_components: int, l1_W=0.0, l2_W=0.0, l1_H=0.0, l2_H=0.0,
+                 group=None):
+        if group is not None and plan_world(group) > 1:
+            raise ValueError("solver='hals' runs on one device (no sharded fit)")
+        if X.dtype == torch.bfloat16:
+            raise TypeError("bfloat16 X is not available for solver='hals': pass float32 or float64")
+        if X.device.type != "cuda":
+            raise ValueError("HALSPlan needs X on a HIP device")
+        if X.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"unsupported X dtype {X.dtype}")
+        if X.dim() != 2:
+            raise ValueError("X must be 2-D")
+        # MUPlan's state, set up here: cnmf_hals_step serves rows (up to 512 features) that the MU
+        # pass, whose partial rows MUPlan.__init__ sizes, does not
+        self.lib = _lib.load()
+        self.X = X.contiguous()
+        self.device = X.device
+        self.n_rows, self.F = (int(s) for s in self.X.shape)
+        self.k = int(n_components)
+        self.xdt = _XDT[X.dtype]
+        self.tc = X.dtype
+        self.l1_W, self.l2_W, self.l1_H, self.l2_H = map(float, (l1_W, l2_W, l1_H, l2_H))
+        self.group, self.world = None, 1
+        self.hals_row_doubles = int(check(self.lib.cnmf_hals_row_doubles(self.F, self.k), "cnmf_hals_row_doubles"))
+        self.hals_rows = int(check(self.lib.cnmf_hals_rows(self.n_rows), "cnmf_hals_rows"))
+        self.KP = int(check(self.lib.cnmf_padded_k(self.k), "cnmf_padded_k"))
+        self.V = self.F + self.k
+        self.n_out = self.k * self.V
+        dev, f64 = self.device, torch.float64
+        self.W = torch.empty((self.n_rows, self.k), dtype=self.tc, device=dev)
+        self.H64 = torch.zeros((self.k, self.F), dtype=f64, device=dev)
+        self.Ht = torch.zeros((self.F, self.KP), dtype=f64, device=dev)
+        self.HHt = torch.zeros((self.KP, self.KP), dtype=f64, device=dev)
+        self.persistent = self.persistent_shape = self.exchange_shape = False
+        self.exchange = self.shard_steps = False
+        self.layouts, self.layout = (), 0
+        self.loss_buf = torch.zeros(1, dtype=f64, device=dev)
+        self.hals_partials = torch.empty(max(self.hals_rows, 1) * self.hals_row_doubles, dtype=torch.float64,
+                                         device=self.device)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.counter = self.ticket  # MUPlan.counters_at_rest
+        self.ctl = self.new_ctl()
+
+    def new_ctl(self, tol: float = 0.0, log_cap: int = 0) -> torch.Tensor:
+        """A zeroed control block with TOL and LOG_CAP set."""
+        import numpy as np
+        host = np.zeros(int(check(self.lib.cnmf_hals_ctl_doubles(int(log_cap)), "cnmf_hals_ctl_doubles")))
+        host[HALS_TOL], host[HALS_LOG_CAP] = tol, log_cap
+        return torch.from_numpy(host).to(self.device)
+
+    def step(self, update_H: bool = True):
+        """One SKCD iteration (a no-op once the control block's STOPPED word is set)."""
+        with torch.cuda.device(self.device):
+            check(self.lib.cnmf_hals_step(
+                _ptr(self.X), self.xdt, _ptr(self.W), _ptr(self.H64), _ptr(self.Ht), _ptr(self.HHt),
+                _ptr(self.hals_partials), self.hals_rows, _ptr(self.ticket), _ptr(self.ctl), self.n_rows,
+                self.F, self.k, self.l1_W, self.l2_W, self.l1_H, self.l2_H,
+                HALS_UPDATE_H if update_H else 0, self._stream()), "cnmf_hals_step")
+
+    def read_ctl(self):
+        """The whole control block as a NumPy array (synchronises)."""
+        return self.ctl.cpu().numpy()
+
+    def frobenius_error(self) -> float:
+        """sqrt(‖X − W·H‖²) (SK:85-129) with the family's own loss launch (cnmf_hals_loss: the MU loss
+        pass does not take every row width the step serves); synchronises."""
+        with torch.cuda.device(self.device):
+            check(self.lib.cnmf_hals_loss(_ptr(self.X), self.xdt, _ptr(self.W), _ptr(self.H64),
+                                          _ptr(self.hals_partials), self.hals_rows, _ptr(self.ticket),
+                                          _ptr(self.loss_buf), self.n_rows, self.F, self.k, self._stream()),
+                  "cnmf_hals_loss")
+        return math.sqrt(max(float(self.loss_buf.item()), 0.0))
+
+    def iterate(self, n_iter: int, update_H: bool = True, pass_events=None):
+        """n_iter launches under the plan's current control block (no host synchronisation)."""
+        if pass_events is not None:
+            raise ValueError("HALSPlan.iterate takes no pass_events")
+        for _ in range(max(n_iter, 0)):
+            self.step(update_H)
+
+    def enable_exchange(self):
+        raise _lib.HipLibraryError("solver='hals' has no in-launch exchange: it runs on one device")
+
+    def prepare_device_tol(self, max_iter, tol, pass_events=None):
+        return None  # run_hals is the driver: the rule is on the device in every launch
+
+    def tune(self, *args, **kwargs) -> dict:
+        return {}  # one kernel
+
+    def describe(self) -> str:
+        return ("hals_step_kernel: one launch per iteration (the W-sweep per sample in fp64, the fp64 partial "
+                "rows, the last-arriving workgroup's H-sweep and stopping rule)")
+
+
+def run_hals(plan: HALSPlan, max_iter: int = 200, tol: float = 1e-4, update_H: bool = True,
+             verbose: int = 0, stretch: int | None = None) -> int:
+    """The driver of `_fit_coordinate_descent` (SK:406-523): launches are enqueued in stretches of
+    `stretch` (default HALS_STRETCH) and the control block is read once per stretch; the stopping
+    rule (violation_init == 0 or violation / violation_init <= tol, SK:509-521) is evaluated on the
+    device after every iteration and turns the stretch's remaining launches into no-ops.  Returns
+    n_iter, the iterations run.  verbose: SKCD's `violation:` lines from the device log."""
+    stretch = HALS_STRETCH if stretch is None else int(stretch)
+    if stretch < 1:
+        raise ValueError(f"stretch must be >= 1, got {stretch}")
+    plan.ctl = plan.new_ctl(tol=float(tol), log_cap=max_iter if verbose else 0)
+    launched = printed = 0
+    host = None
+    while launched < max_iter:
+        n = min(stretch, max_iter - launched)
+        with trace_range(f"cnmf:hals iterations {launched + 1}..{launched + n}"):
+            for _ in range(n):
+                plan.step(update_H)
+        launched += n
+        host = plan.read_ctl()
+        if verbose and host[HALS_VIOL_INIT] != 0:
+            for i in range(printed, int(host[HALS_NLOG])):
+                print("violation:", host[HALS_LOG + i] / host[HALS_VIOL_INIT])
+            printed = int(host[HALS_NLOG])
+        if host[HALS_STOPPED] != 0:
+            if verbose and host[HALS_VIOL_INIT] != 0:
+                print("Converged at iteration", int(host[HALS_ITERS_DONE]) + 1)
+            break
+    return int(host[HALS_ITERS_DONE]) if host is not None else 0
+
+
 class ALSPlan(MUPlan):
     """Device state of the constrained-ALS variant (spec and oracle:
     oracle/als_ref.py, DESIGN.md §Constrained ALS).

@@ -50,7 +50,8 @@ enum cnmf_pass_flags {
   CNMF_PASS_LOSS = 4        /* only: partial sums of ‖X − W·H‖² (SK:85-129), one per block   */
 };
 
-/* ABI version (major*100 + minor) and last error message of the calling thread. */
+/* ABI version (major*100 + minor) and last error message of the calling thread.  303 also covers
+ * the cnmf_hals_* entry points: they only add symbols, no existing signature or layout changed. */
 int cnmf_abi_version(void);
 const char* cnmf_last_error(void);
 
@@ -429,6 +430,50 @@ int cnmf_mb_step(const void* X, int x_dtype, void* W, double* H64, double* Ht, d
 int cnmf_mb_solve_w(const void* X, int x_dtype, void* W, const double* Ht, const double* HHt, double* partials,
                     int64_t n_parts, uint32_t* counter, double* ctl, int64_t n_rows, int n_features, int k,
                     double l1_W, double l2_W, void* stream);
+
+/* ---- solver='hals': scikit-learn 1.7.2's coordinate-descent solver with shuffle=False (SKCD =
+ * `_fit_coordinate_descent`, sklearn/decomposition/_nmf.py:376-523: the loop and its stopping rule
+ * SK:406-523 (the rule SK:509-521), one half iteration `_update_coordinate_descent` SK:376-403, the sweep
+ * `_update_cdnmf_fast` of _cdnmf_fast.pyx — the "Fast HALS" of Cichocki & Phan) with the stopping
+ * rule on the device (cnmf_amd/solver.py HALSPlan / run_hals).  fp32 or fp64 X, W in
+ * X's type, 1 <= k <= 16, 1 <= n_features <= 512, any n_rows >= 1, one GPU.
+ *
+ * A sweep of rows R (n x k) against G (k x k, l2 added to its diagonal) and C (n x k, l1 subtracted):
+ * for every row i and t = 0 .. k-1 in order: grad = -C[i,t] + sum_r G[t,r] R[i,r] (the entries r < t
+ * already updated); pg = min(0, grad) if R[i,t] == 0 else grad; violation += |pg|; if G[t,t] != 0:
+ * R[i,t] = max(R[i,t] - grad / G[t,t], 0).  No clamp of small values and no epsilon.
+ *
+ * cnmf_hals_step: ONE launch = one SKCD iteration over X, W (n_rows rows):
+ *   the W-sweep (R = W, C = X Ht, G = HHt, l1_W / l2_W) of every sample in fp64, w' rounded once to
+ *   W's type; with CNMF_HALS_UPDATE_H the H-sweep (R = H^T, C = X^T W', G = W'^T W', l1_H / l2_H) in
+ *   fp64, H64 / Ht / HHt refreshed; violation = the sum over both sweeps; ITERS_DONE advances;
+ *   iteration 1 stores VIOL_INIT; STOPPED is set when VIOL_INIT == 0 or violation / VIOL_INIT <= TOL
+ *   (tested every iteration, also for TOL = 0).  Every launch first reads ctl[CNMF_HALS_STOPPED]:
+ *   once it is set, the launch writes nothing, so a stretch of iterations can be enqueued without a
+ *   host round trip.  The same inputs give the same bits (every sum has a fixed order).
+ *   partials: cnmf_hals_rows(n_rows) rows of cnmf_hals_row_doubles(F, k) doubles
+ *   [W'^T X | W'^T W' | sum |pg| | pad] (no memset needed); counter: one zeroed uint32, left zero.
+ * ctl: cnmf_hals_ctl_doubles(log_cap) doubles, zeroed by the caller, who then sets CNMF_HALS_TOL and
+ *   CNMF_HALS_LOG_CAP; the launches maintain the rest, and from CNMF_HALS_LOG up to log_cap entries,
+ *   the violation of every iteration (NLOG counts them).
+ * The sizing helpers are host only (no HIP call, no device needed). */
+enum cnmf_hals_flags { CNMF_HALS_UPDATE_H = 1 };
+enum cnmf_hals_slots {
+  CNMF_HALS_STOPPED = 0, CNMF_HALS_ITERS_DONE = 1, CNMF_HALS_VIOL_INIT = 2, CNMF_HALS_VIOL_LAST = 3,
+  CNMF_HALS_TOL = 4, CNMF_HALS_LOG_CAP = 5, CNMF_HALS_NLOG = 6, CNMF_HALS_LOG = 16
+};
+int64_t cnmf_hals_rows(int64_t n_rows);
+int64_t cnmf_hals_row_doubles(int n_features, int k);
+int64_t cnmf_hals_ctl_doubles(int64_t log_cap);
+int cnmf_hals_step(const void* X, int x_dtype, void* W, double* H64, double* Ht, double* HHt, double* partials,
+                   int64_t n_parts, uint32_t* counter, double* ctl, int64_t n_rows, int n_features, int k,
+                   double l1_W, double l2_W, double l1_H, double l2_H, int flags, void* stream);
+/* out[0] = ||X - W H||^2 (SK:85-129 before the square root) in fp64 from H64, for every shape
+ * cnmf_hals_step serves (cnmf_mu_sample_pass's loss form does not take rows as wide: F = 300 at
+ * k = 16 in fp64, F = 512).  partials: cnmf_hals_rows(n_rows) doubles (the step's buffer will do);
+ * counter: one zeroed uint32, left zero; fixed-order sums. */
+int cnmf_hals_loss(const void* X, int x_dtype, const void* W, const double* H64, double* partials, int64_t n_parts,
+                   uint32_t* counter, double* out, int64_t n_rows, int n_features, int k, void* stream);
 
 #ifdef __cplusplus
 }
