@@ -14,7 +14,8 @@ from ._lib import HipLibraryError
 from ._trace import tracing
 from .api import NMF, ConvergenceWarning, factorise, fit, non_negative_factorization
 from .minibatch import MiniBatchNMF
+from .spa import spa, spa_init
 
 __version__ = "0.1.0"
-__all__ = ["factorise", "fit", "non_negative_factorization", "NMF", "MiniBatchNMF", "ConvergenceWarning",
-           "HipLibraryError", "tracing", "__version__"]
+__all__ = ["factorise", "fit", "non_negative_factorization", "NMF", "MiniBatchNMF", "spa", "spa_init",
+           "ConvergenceWarning", "HipLibraryError", "tracing", "__version__"]

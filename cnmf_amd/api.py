@@ -34,7 +34,7 @@ class ConvergenceWarning(UserWarning):
     """Custom warning to capture convergence problems (the role of
     sklearn.exceptions.ConvergenceWarning; the product path imports nothing from sklearn)."""
 
-_INITS = {"random", "nndsvd", "nndsvda", "nndsvdar", "custom", None}
+_INITS = {"random", "nndsvd", "nndsvda", "nndsvdar", "spa", "custom", None}
 
 
 def _torch():
@@ -122,7 +122,7 @@ def _validate_params(n_components, init, solver, beta_loss, tol, max_iter, alpha
                          f"None or 'auto'. Got {n_components!r} instead.")
     if init not in _INITS:
         raise ValueError(f"The 'init' parameter must be a str among {{'custom', 'nndsvd', "
-                         f"'nndsvda', 'nndsvdar', 'random'}} or None. Got {init!r} instead.")
+                         f"'nndsvda', 'nndsvdar', 'random', 'spa'}} or None. Got {init!r} instead.")
     if solver not in ("mu", "als", "hals"):
         raise ValueError(f"solver={solver!r} is not available: this build implements the "
                          "multiplicative-update solver ('mu') and the constrained ALS ('als'), "
@@ -201,6 +201,23 @@ def _validate_hals(solver, shuffle, devices=None):
         raise ValueError("devices= is not available for solver='hals': it runs on one device.")
 
 
+def _validate_spa(init, weights=None, devices=None, group=None, streamed=False):
+    """init='spa' (cnmf_amd.spa) selects rows of the whole X on one device."""
+    if init != "spa":
+        return
+    if weights is not None:
+        raise ValueError("init='spa' is not available with weights=: a masked entry would take part in "
+                         "the selection.")
+    if devices is not None:
+        raise ValueError("init='spa' is not available with devices=: the selection runs on one device.")
+    if group is not None:
+        raise ValueError("init='spa' is not available for a sharded fit (group=): the selection needs every "
+                         "row of X on one device.")
+    if streamed:
+        raise ValueError("init='spa' is not available with a memory_budget that streams X: the selection "
+                         "needs X on the device.")
+
+
 _TORCH_DT = {}  # numpy scalar type -> torch dtype, filled on first use
 GPU_INIT_MIN_ROWS = 65536
 
@@ -249,6 +266,10 @@ def _initial_factors(X, k, init, random_state, device, as_torch, group, host_onl
     if not _TORCH_DT:
         _TORCH_DT.update({np.float32: torch.float32, np.float64: torch.float64})
     n_samples, n_features = X.shape
+    if init == "spa":  # never chosen by init=None; random_state is ignored (SPA is deterministic)
+        _validate_spa(init, group=group)
+        from .spa import spa_init
+        return spa_init(X, k, device=device)
     resolved = init
     if init is None:
         resolved = "nndsvda" if k <= min(n_samples, n_features) else "random"
@@ -277,6 +298,8 @@ def _resolve(X, W, H, n_components, init, update_H, alpha_W, alpha_H, l1_ratio, 
     if solver == "hals" and as_torch and X.dtype == torch.bfloat16:
         raise TypeError("bfloat16 X is not available for solver='hals': pass float32 or float64")
     streamed = _streamed(X, as_torch, memory_budget, solver, Mw)
+    if update_H:
+        _validate_spa(init, weights=weights, group=group, streamed=streamed)
     n_samples, n_features = X.shape
     k = n_components
     if k is None:
@@ -450,6 +473,11 @@ def factorise(X, W=None, H=None, n_components="auto", *, init=None, update_H=Tru
     `init_device` ('auto' | 'host' | 'gpu'): where init=None / 'nndsvd*' computes its SVD start —
     see `_initial_factors`; 'auto' reproduces sklearn's start for float32 X (host restatement) and
     runs the passes over X on the GPU for float64 X.
+    init='spa' (beyond sklearn's names; never chosen by init=None): the successive projection
+    start of cnmf_amd.spa — H0 = k rows of X picked on the device, W0 = max(X·pinv(H0),
+    X.mean()/100); deterministic (random_state is ignored); every solver; float32 / float64 X on
+    one device, n_components <= min(n_samples, n_features); no weights, devices= or streaming.
+    It assumes that nearly pure rows exist in X.
     `devices` (list of HIP device indices or torch devices; None = one device): split the rows
     over several GPUs driven from THIS process (cnmf_amd.multidevice): one stream and
     one persistent launch per device per stretch, the per-device [WᵀX | WᵀW] summed inside the
@@ -460,6 +488,7 @@ def factorise(X, W=None, H=None, n_components="auto", *, init=None, update_H=Tru
     _validate_als(solver, alpha_W, alpha_H, sum_to_one, smoothness)
     _validate_hals(solver, shuffle, devices)
     _validate_init_device(init_device)
+    _validate_spa(init, weights=weights, devices=devices)
     if devices is not None:
         from .multidevice import factorise_devices
         return factorise_devices(X, W, H, n_components, devices=devices, init=init, update_H=update_H,

@@ -7912,4 +7912,5 @@ int cnmf_wmu_basis_update(const double* AD, double* H64, int n_features, int k, 
 #include "init.hip"
 #include "minibatch.hip"
 #include "hals.hip"
+#include "spa.hip"
 #endif

@@ -475,6 +475,49 @@ int cnmf_hals_step(const void* X, int x_dtype, void* W, double* H64, double* Ht,
 int cnmf_hals_loss(const void* X, int x_dtype, const void* W, const double* H64, double* partials, int64_t n_parts,
                    uint32_t* counter, double* out, int64_t n_rows, int n_features, int k, void* stream);
 
+/* ---- init='spa': the successive projection algorithm (SPA; Araujo et al. 2001, Gillis & Vavasis
+ * 2014) as a start: k rows of X, the "purest" spectra, become H0 (cnmf_amd/spa.py; the spec is
+ * tests/spa_ref.py).  fp32 or fp64 X, 1 <= k <= 16, 1 <= n_features <= 512, any
+ * n_rows >= 1, one GPU.  Rows need not be a multiple of 16 bytes.
+ *
+ * With y_i = s_i x_i (CNMF_SPA_NORM_L1: s_i = 1 / sum_f x_if, 0 for an all-zero row; CNMF_SPA_NORM_NONE:
+ * s_i = 1), step j picks the smallest row p_j attaining max_i ||r_i||^2, r_i = y_i - sum_{t<j} q_t (q_t . y_i)
+ * formed explicitly in fp64, and q_j = r_{p_j} / ||r_{p_j}||, orthogonalised against q_0 .. q_{j-1} once
+ * more (Gram-Schmidt twice).
+ *
+ * cnmf_spa_step: ONE launch = step j (0 <= j < k; enqueue j = 0 .. k-1 back to back):
+ *   one read-only pass over X, every row's score by the same operations in the same order wherever
+ *   the row sits (identical rows give identical bits); the last-arriving workgroup takes the best of
+ *   the per-workgroup partials in row order (the lower row on a tie), re-reads row p_j and writes
+ *   Q[j] (Q: k x F fp64, rows 0 .. j-1 are read), ctl[CNMF_SPA_IDX + j] = p_j, ctl[CNMF_SPA_RHO + j] =
+ *   ||r_{p_j}|| / YMAX and STEPS_DONE = j + 1; step 0 also writes SUM_X (the sum of X's entries, fixed
+ *   order) and YMAX = max_i ||y_i||.  When RHO[j] <= RANK_TOL the rank of X is exhausted: STOPPED is
+ *   set and neither IDX[j] nor Q[j] nor STEPS_DONE is written.  Step k-1 sets STOPPED too.  Every
+ *   launch first reads ctl[CNMF_SPA_STOPPED]: once it is set, the launch writes nothing.  The same
+ *   inputs give the same bits.
+ *   partials: cnmf_spa_rows(n_rows) rows of cnmf_spa_row_doubles() doubles [best score | its row |
+ *   sum of the workgroup's entries | pad] (no memset needed); counter: one zeroed uint32, left zero;
+ *   scores: null, or n_rows doubles that receive every row's score of this step (tests).
+ * ctl: cnmf_spa_ctl_doubles(k) doubles, zeroed by the caller, who then sets CNMF_SPA_RANK_TOL; the
+ *   launches maintain the rest.
+ * cnmf_spa_start_w: W = max(X M, floor) in one pass (M: F x k fp64, row-major; the products in fp64,
+ *   rounded once to W's type, fp32 or fp64; W: n_rows x k).  Same shape limits (cnmf_init_xm stops
+ *   at n_features = 96).
+ * The sizing helpers are host only (no HIP call, no device needed). */
+enum cnmf_spa_norm { CNMF_SPA_NORM_NONE = 0, CNMF_SPA_NORM_L1 = 1 };
+enum cnmf_spa_slots {
+  CNMF_SPA_STOPPED = 0, CNMF_SPA_STEPS_DONE = 1, CNMF_SPA_SUM_X = 2, CNMF_SPA_YMAX = 3, CNMF_SPA_RANK_TOL = 4,
+  CNMF_SPA_IDX = 8, CNMF_SPA_RHO = 24
+};
+int64_t cnmf_spa_rows(int64_t n_rows);
+int64_t cnmf_spa_row_doubles(void);
+int64_t cnmf_spa_ctl_doubles(int k);
+int cnmf_spa_step(const void* X, int x_dtype, double* Q, double* partials, int64_t n_parts, uint32_t* counter,
+                  double* ctl, double* scores, int64_t n_rows, int n_features, int k, int j, int normalise,
+                  void* stream);
+int cnmf_spa_start_w(const void* X, int x_dtype, const double* M, double floor, void* W, int w_dtype, int64_t n_rows,
+                     int n_features, int k, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
