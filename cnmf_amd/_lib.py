@@ -123,6 +123,9 @@ _SIGS = {
     "cnmf_hals_ctl_doubles": (_i64, [_i64]),
     "cnmf_hals_step": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32,
                               _f64, _f64, _f64, _f64, _i32, _vp]),
+    "cnmf_hals_shard_step": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32,
+                                    _f64, _f64, _vp]),
+    "cnmf_hals_basis": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f64, _f64, _i32, _vp]),
     "cnmf_hals_loss": (_i32, [_vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp]),
     "cnmf_spa_rows": (_i64, [_i64]),
     "cnmf_spa_row_doubles": (_i64, []),

@@ -1,4 +1,5 @@
-// hals.hip — solver='hals': hals_step_kernel, hals_loss_kernel and the cnmf_hals_* entry points.
+// hals.hip — solver='hals': hals_step_kernel, its sharded form (hals_shard_step_kernel, hals_basis_kernel),
+// hals_loss_kernel and the cnmf_hals_* entry points.
 #include "common.hpp"
 #include "host.hpp"
 
@@ -26,6 +27,9 @@ namespace cnmf {
 // inputs give the same bits.  The tile arithmetic is mb_step_kernel's (minibatch.hip), duplicated:
 // a workgroup is TEAMS teams of 256 threads, each staging and processing its own tiles.
 // General tile (1 <= F <= 512, 1 <= k <= 16, fp32 / fp64 X): not tuned per shape.
+// Row shards (one rank per GPU) split the launch where the sum over all rows is needed: the last
+// arriver of hals_shard_step_kernel writes the summed row to acc and stops there, the host
+// all-reduces acc over the ranks, and hals_basis_kernel (one workgroup) runs the tail from it.
 // ------------------------------------------------------------------------------------------------
 namespace hals {
 constexpr int MAX_BLOCKS = 256;   // partial rows of a launch, at most (one tail workgroup sums them)
@@ -267,6 +271,131 @@ __device__ __forceinline__ void sum_rows(const double* partials, int G, int RL, 
   __syncthreads();
 }
 
+// front and tail: hals_step_kernel's body before and after its sum_rows, duplicated for the
+// sharded form's two kernels (sharing them with hals_step_kernel changed its instances' code; as
+// with the tile arithmetic, the copy keeps the shipped kernel as it was).  Keep them in step.
+// front — after the gate: the W-sweep of this workgroup's rows, its partial row and the ticket.
+// True in every thread of the last-arriving workgroup.
+template <typename TX, int KP, int TEAMS>
+__device__ __forceinline__ bool front(const Args& a, unsigned char* smem) {
+  constexpr int NTB = NT * TEAMS;
+  double* red = reinterpret_cast<double*>(smem);           // [16]
+  int* flag = reinterpret_cast<int*>(smem + 128);
+  double* un = reinterpret_cast<double*>(smem + MISC);     // the union region
+  const int tid = threadIdx.x;
+  const int team = tid / NT, t = tid - team * NT;
+  const int F = a.F, k = a.k;
+  const int kF = k * F, kk = k * k;
+  const int RL = row_doubles(F, k);
+  const int FL = feat_lanes(F), RG = NT / FL;
+  const int rg = t / FL, fl = t - rg * FL;
+  const int64_t rpb = rows_per_block(a.n_rows);
+  const int64_t r0 = (int64_t)blockIdx.x * rpb;
+  const int64_t r1 = r0 + rpb < a.n_rows ? r0 + rpb : a.n_rows;
+
+  double acc[2][KP], bacc[KP], viol = 0.0;
+#pragma unroll
+  for (int j = 0; j < KP; ++j) acc[0][j] = acc[1][j] = bacc[j] = 0.0;
+  pass<TX, KP, TEAMS>(a, smem, r0, r1, acc, bacc, viol);
+
+  // the (team, row group) accumulators through LDS (over the pass's buffers), summed in order
+  const int SL = kF + kk;  // per group: A | B
+  const int NG = TEAMS * RG;
+  __syncthreads();
+  {
+    double* mine = un + (size_t)(team * RG + rg) * SL;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int f = fl + s * FL;
+      if (f >= F) continue;
+#pragma unroll
+      for (int j = 0; j < KP; ++j)
+        if (j < k) mine[j * F + f] = acc[s][j];
+    }
+    if (fl < k) {
+#pragma unroll
+      for (int j = 0; j < KP; ++j)
+        if (j < k) mine[kF + fl * k + j] = bacc[j];
+    }
+  }
+  const double bviol = block_sum(viol, red);  // its barriers also publish the scratch
+  double* prow = a.partials + (size_t)blockIdx.x * RL;
+  for (int e = tid; e < kF + kk; e += NTB) {
+    double s = 0.0;
+    for (int g = 0; g < NG; ++g) s += un[(size_t)g * SL + e];
+    st_agent(prow + e, s);
+  }
+  if (tid == 0) {
+    st_agent(prow + kF + kk, bviol);
+    for (int e = kF + kk + 1; e < RL; ++e) st_agent(prow + e, 0.0);
+  }
+  return last_arriver(a.counter, flag);
+}
+
+// The tail of an iteration, run by one workgroup of NTB threads from the summed row S (LDS, [RL]:
+// A | B | Σ|pg| of the W-sweep over all rows): with CNMF_HALS_UPDATE_H the H-sweep with a lane per
+// feature into Hn (LDS, [k][F]; KP·KP doubles of scratch follow it) and H64 / Ht / HHt refreshed;
+// always the control block's update and the stopping rule.  The H-sweep, H64, Ht and HHt do not
+// depend on NTB; the H-sweep's violation is summed per thread (features tid, tid + NTB), then by
+// block_sum, so its last bits depend on NTB only when F > NTB.
+template <int KP, int NTB>
+__device__ __forceinline__ void tail(const Args& a, double* S, double* Hn, double* red) {
+  const int tid = threadIdx.x;
+  const int F = a.F, k = a.k;
+  const int kF = k * F, kk = k * k;
+  const bool update_h = a.flags & CNMF_HALS_UPDATE_H;
+  double vh = 0.0;
+  if (update_h) {
+    double* sG = Hn + kF;  // [KP][KP]: W'ᵀW', l2_H on the diagonal, zero beyond k
+    for (int e = tid; e < KP * KP; e += NTB) {
+      const int j = e / KP, m = e - j * KP;
+      sG[e] = (j < k && m < k) ? S[kF + j * k + m] + (j == m ? a.l2H : 0.0) : 0.0;
+    }
+    __syncthreads();
+    for (int f = tid; f < F; f += NTB) {  // a lane per feature: the row f of Hᵀ
+      double c[KP], h[KP];
+#pragma unroll
+      for (int j = 0; j < KP; ++j) {
+        c[j] = j < k ? S[j * F + f] - a.l1H : 0.0;
+        h[j] = j < k ? a.H64[j * F + f] : 0.0;
+      }
+      vh += sweep_row<KP>(sG, c, h, k);
+#pragma unroll
+      for (int j = 0; j < KP; ++j)
+        if (j < k) Hn[j * F + f] = h[j];
+    }
+    vh = block_sum(vh, red);  // its barriers: every read of the old H64 is done, Hn is written
+    for (int e = tid; e < kF; e += NTB) a.H64[e] = Hn[e];
+    for (int e = tid; e < F * KP; e += NTB) {
+      const int f = e / KP, j = e - f * KP;
+      a.Ht[e] = j < k ? Hn[j * F + f] : 0.0;
+    }
+    const int lane = tid & 63, wave = tid >> 6;
+    for (int e = wave; e < KP * KP; e += NTB / 64) {
+      const int j = e / KP, m = e - j * KP;
+      double v = 0.0;
+      if (j < k && m < k)
+        for (int f = lane; f < F; f += 64) v = fma(Hn[j * F + f], Hn[m * F + f], v);
+      v = wave_sum(v);
+      if (lane == 0) a.HHt[e] = v;
+    }
+  }
+  if (tid != 0) return;
+  double* c = a.ctl;
+  const double violation = S[kF + kk] + vh;  // SKCD: the sum over both sweeps
+  const double it = c[CNMF_HALS_ITERS_DONE] + 1.0;
+  c[CNMF_HALS_ITERS_DONE] = it;
+  if (it == 1.0) c[CNMF_HALS_VIOL_INIT] = violation;
+  const double init = c[CNMF_HALS_VIOL_INIT];
+  c[CNMF_HALS_VIOL_LAST] = violation;
+  const int64_t cap = (int64_t)c[CNMF_HALS_LOG_CAP], n = (int64_t)c[CNMF_HALS_NLOG];
+  if (n < cap) {
+    c[CNMF_HALS_LOG + n] = violation;
+    c[CNMF_HALS_NLOG] = (double)(n + 1);
+  }
+  if (init == 0.0 || violation / init <= c[CNMF_HALS_TOL]) st_agent(c + CNMF_HALS_STOPPED, 1.0);
+}
+
 }  // namespace hals
 
 template <typename TX, int KP, int TEAMS>
@@ -384,6 +513,40 @@ __global__ __launch_bounds__(NT * TEAMS) void hals_step_kernel(hals::Args a) {
   if (init == 0.0 || violation / init <= c[CNMF_HALS_TOL]) st_agent(c + CNMF_HALS_STOPPED, 1.0);
 }
 
+// The sharded iteration's first launch (cnmf_hals_shard_step): hals_step_kernel up to the summed
+// row, which the last arriver writes to acc for the all-reduce over the ranks.  No H-sweep, and no
+// write to H64 / Ht / HHt / ctl (a.H64 is not read).
+template <typename TX, int KP, int TEAMS>
+__global__ __launch_bounds__(NT * TEAMS) void hals_shard_step_kernel(hals::Args a, double* acc) {
+  using namespace hals;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  if (ld_agent(a.ctl + CNMF_HALS_STOPPED) != 0.0) return;  // the gate
+  if (!front<TX, KP, TEAMS>(a, smem)) return;
+  const int RL = row_doubles(a.F, a.k);
+  double* S = reinterpret_cast<double*>(smem + MISC);
+  sum_rows(a.partials, (int)gridDim.x, RL, S);
+  for (int c = threadIdx.x; c < RL; c += NT * TEAMS) acc[c] = S[c];
+}
+
+// The sharded iteration's second launch (cnmf_hals_basis), one workgroup: the step's tail from the
+// all-reduced row.  Every rank runs it on the same acc, H64 and ctl, so every rank gets the same H
+// and takes the same decision.
+template <int KP>
+__global__ __launch_bounds__(NT) void hals_basis_kernel(const double* acc, double* H64, double* Ht, double* HHt,
+                                                        double* ctl, int F, int k, double l1H, double l2H, int flags) {
+  using namespace hals;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  if (ld_agent(ctl + CNMF_HALS_STOPPED) != 0.0) return;  // the gate
+  const int RL = row_doubles(F, k);
+  double* un = reinterpret_cast<double*>(smem + MISC);
+  double* S = un;
+  double* Hn = un + RL;
+  for (int c = threadIdx.x; c < RL; c += NT) S[c] = acc[c];
+  __syncthreads();
+  const Args a{nullptr, nullptr, H64, Ht, HHt, nullptr, nullptr, ctl, 0, F, k, 0.0, 0.0, l1H, l2H, flags};
+  tail<KP, NT>(a, S, Hn, reinterpret_cast<double*>(smem));
+}
+
 // ‖X − W·H‖² in fp64 from the fp64 H (SK:85-129 before the square root), for every shape the step
 // serves: the workgroups and their rows as the step's, a wave per row and a lane per feature, H
 // staged in LDS; one double per workgroup, the last arriver sums them in row order into out[0].
@@ -434,14 +597,19 @@ size_t hals_lds(int F, int k, int KP, int xbytes, int teams) {
   return MISC + std::max(pass, std::max(scratch, tail));
 }
 
+// acc null: the one-launch step; else the sharded iteration's first launch, which leaves the summed row in acc
 template <typename TX, int KP, int TEAMS>
-int hals_launch_t(const hals::Args& a, hipStream_t hs) {
+int hals_launch_t(const hals::Args& a, double* acc, hipStream_t hs) {
   const size_t lds = hals_lds(a.F, a.k, KP, (int)sizeof(TX), TEAMS);
   if (lds > kMaxLds) return set_err(CNMF_ERR_UNSUPPORTED, "hals step needs %zu bytes of LDS", lds);
-  const void* fn = reinterpret_cast<const void*>(&hals_step_kernel<TX, KP, TEAMS>);
+  const void* fn = acc ? reinterpret_cast<const void*>(&hals_shard_step_kernel<TX, KP, TEAMS>)
+                       : reinterpret_cast<const void*>(&hals_step_kernel<TX, KP, TEAMS>);
   if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const dim3 grid((unsigned)hals::blocks(a.n_rows)), block(NT * TEAMS);
-  hipLaunchKernelGGL((hals_step_kernel<TX, KP, TEAMS>), grid, block, lds, hs, a);
+  if (acc)
+    hipLaunchKernelGGL((hals_shard_step_kernel<TX, KP, TEAMS>), grid, block, lds, hs, a, acc);
+  else
+    hipLaunchKernelGGL((hals_step_kernel<TX, KP, TEAMS>), grid, block, lds, hs, a);
   HIP_CHECK(hipGetLastError());
   return CNMF_OK;
 }
@@ -449,7 +617,7 @@ int hals_launch_t(const hals::Args& a, hipStream_t hs) {
 // teams per workgroup: as many as the registers of the instance (KP) and the LDS allow, and no
 // more than the workgroup has tiles
 template <typename TX>
-int hals_launch_k(const hals::Args& a, hipStream_t hs) {
+int hals_launch_k(const hals::Args& a, double* acc, hipStream_t hs) {
   const int KP = a.k <= 4 ? 4 : (a.k <= 8 ? 8 : 16);
   const int64_t tiles = (hals::rows_per_block(a.n_rows) + hals::tile_rows(a.F, (int)sizeof(TX)) - 1) /
                         hals::tile_rows(a.F, (int)sizeof(TX));
@@ -457,15 +625,15 @@ int hals_launch_k(const hals::Args& a, hipStream_t hs) {
     return tiles >= teams && hals_lds(a.F, a.k, KP, (int)sizeof(TX), teams) <= kMaxLds;
   };
   if (KP == 4) {
-    if (fits(4)) return hals_launch_t<TX, 4, 4>(a, hs);
-    if (fits(2)) return hals_launch_t<TX, 4, 2>(a, hs);
-    return hals_launch_t<TX, 4, 1>(a, hs);
+    if (fits(4)) return hals_launch_t<TX, 4, 4>(a, acc, hs);
+    if (fits(2)) return hals_launch_t<TX, 4, 2>(a, acc, hs);
+    return hals_launch_t<TX, 4, 1>(a, acc, hs);
   }
   if (KP == 8) {
-    if (fits(2)) return hals_launch_t<TX, 8, 2>(a, hs);
-    return hals_launch_t<TX, 8, 1>(a, hs);
+    if (fits(2)) return hals_launch_t<TX, 8, 2>(a, acc, hs);
+    return hals_launch_t<TX, 8, 1>(a, acc, hs);
   }
-  return hals_launch_t<TX, 16, 1>(a, hs);
+  return hals_launch_t<TX, 16, 1>(a, acc, hs);
 }
 
 }  // namespace
@@ -490,7 +658,7 @@ int64_t cnmf_hals_ctl_doubles(int64_t log_cap) {
 
 namespace {
 
-// the checks the two launches share, after their null-pointer checks
+// the checks the launches over X share, after their null-pointer checks
 int hals_check(const void* X, int x_dtype, const void* W, int64_t n_parts, int64_t n_rows, int n_features, int k) {
   if (n_rows < 1 || n_features < 1 || k < 1)
     return set_err(CNMF_ERR_SHAPE, "invalid shape: n_rows=%lld F=%d k=%d", (long long)n_rows, n_features, k);
@@ -516,6 +684,18 @@ int hals_loss_t(const void* X, const void* W, const double* H64, double* partial
   return CNMF_OK;
 }
 
+// the tail's LDS (hals_lds's `tail` term): S, Hn and the H-sweep's G
+template <int KP>
+int hals_basis_t(const double* acc, double* H64, double* Ht, double* HHt, double* ctl, int F, int k, double l1H,
+                 double l2H, int flags, hipStream_t hs) {
+  const size_t lds = hals::MISC + ((size_t)hals::row_doubles(F, k) + (size_t)k * F + KP * KP) * 8;
+  const void* fn = reinterpret_cast<const void*>(&hals_basis_kernel<KP>);
+  if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((hals_basis_kernel<KP>), dim3(1), dim3(NT), lds, hs, acc, H64, Ht, HHt, ctl, F, k, l1H, l2H, flags);
+  HIP_CHECK(hipGetLastError());
+  return CNMF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -529,7 +709,34 @@ int cnmf_hals_step(const void* X, int x_dtype, void* W, double* H64, double* Ht,
   if (const int st = hals_check(X, x_dtype, W, n_parts, n_rows, n_features, k)) return st;
   const hals::Args a{X, W, H64, Ht, HHt, partials, counter, ctl, n_rows, n_features, k, l1_W, l2_W, l1_H, l2_H, flags};
   hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
-  return x_dtype == CNMF_F32 ? hals_launch_k<float>(a, hs) : hals_launch_k<double>(a, hs);
+  return x_dtype == CNMF_F32 ? hals_launch_k<float>(a, nullptr, hs) : hals_launch_k<double>(a, nullptr, hs);
+}
+
+int cnmf_hals_shard_step(const void* X, int x_dtype, void* W, const double* Ht, const double* HHt, double* partials,
+                         int64_t n_parts, uint32_t* counter, const double* ctl, double* acc, int64_t n_rows,
+                         int n_features, int k, double l1_W, double l2_W, void* stream) {
+  if (!X || !W || !Ht || !HHt || !partials || !counter || !ctl || !acc)
+    return set_err(CNMF_ERR_ARG, "null pointer argument");
+  if (const int st = hals_check(X, x_dtype, W, n_parts, n_rows, n_features, k)) return st;
+  if (reinterpret_cast<uintptr_t>(acc) & 15) return set_err(CNMF_ERR_ALIGN, "acc must be 16-byte aligned");
+  const hals::Args a{X, W, nullptr, const_cast<double*>(Ht), const_cast<double*>(HHt), partials, counter,
+                     const_cast<double*>(ctl), n_rows, n_features, k, l1_W, l2_W, 0.0, 0.0, 0};
+  hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
+  return x_dtype == CNMF_F32 ? hals_launch_k<float>(a, acc, hs) : hals_launch_k<double>(a, acc, hs);
+}
+
+int cnmf_hals_basis(const double* acc, double* H64, double* Ht, double* HHt, double* ctl, int n_features, int k,
+                    double l1_H, double l2_H, int flags, void* stream) {
+  if (!acc || !H64 || !Ht || !HHt || !ctl) return set_err(CNMF_ERR_ARG, "null pointer argument");
+  if (flags & ~CNMF_HALS_UPDATE_H) return set_err(CNMF_ERR_ARG, "flags %d", flags);
+  if (n_features < 1 || k < 1) return set_err(CNMF_ERR_SHAPE, "invalid shape: F=%d k=%d", n_features, k);
+  if (k > hals::KMAX || n_features > hals::FMAX)
+    return set_err(CNMF_ERR_UNSUPPORTED, "hals: k=%d (1..%d), n_features=%d (1..%d)", k, hals::KMAX, n_features, hals::FMAX);
+  if (reinterpret_cast<uintptr_t>(acc) & 15) return set_err(CNMF_ERR_ALIGN, "acc must be 16-byte aligned");
+  hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
+  return k <= 4 ? hals_basis_t<4>(acc, H64, Ht, HHt, ctl, n_features, k, l1_H, l2_H, flags, hs)
+       : k <= 8 ? hals_basis_t<8>(acc, H64, Ht, HHt, ctl, n_features, k, l1_H, l2_H, flags, hs)
+                : hals_basis_t<16>(acc, H64, Ht, HHt, ctl, n_features, k, l1_H, l2_H, flags, hs);
 }
 
 int cnmf_hals_loss(const void* X, int x_dtype, const void* W, const double* H64, double* partials, int64_t n_parts,

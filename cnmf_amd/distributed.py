@@ -5,6 +5,8 @@ the fused pass on its shard, reduces its per-workgroup partials to the k·(F+k) 
 [WᵀX | WᵀW], ONE all_reduce(SUM) combines them over xGMI (backend "nccl" is RCCL on ROCm), and every
 rank applies the identical fp64 basis update — no broadcast.  The error check every 10 iterations
 all-reduces one double.  The sharding is exact: Σ_p W_pᵀX_p = WᵀX (tests/test_distributed.py).
+solver='hals' shards the same way: the W-sweep is local to a sample and the H-sweep needs only
+W'ᵀX, W'ᵀW' and the W-sweep's violation summed over all rows (tests/hals_shard_ref.py).
 
     import torch.distributed as dist
     dist.init_process_group("nccl")
@@ -19,7 +21,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .solver import ALSPlan, MUPlan, WeightedMUPlan, run_mu
+from .solver import ALSPlan, HALSPlan, MUPlan, WeightedMUPlan, run_hals, run_mu
 
 __all__ = ["shard_bounds", "factorise_sharded"]
 
@@ -63,9 +65,26 @@ def factorise_sharded(X_shard, W_shard, H0, *, max_iter=200, tol=1e-4, l1_reg_W=
     solver='als': the constrained ALS (sum_to_one, smoothness), its [WᵀX | WᵀW]
     all-reduced before every H-step.  Both take exchange=True (fp32, F = 81, k = 4, rows a multiple
     of 16): one persistent launch per rank with the all-reduce inside it.
+    solver='hals': sklearn's coordinate-descent sweep (shuffle=False) and its stopping rule (fp32 /
+    fp64 X, k <= 16, F <= 512; l1 / l2 terms as for MU): per iteration the shard's W-sweep and summed
+    row [W'ᵀX | W'ᵀW' | Σ|pg|], one all-reduce, then the identical H-sweep and rule on every rank
+    (HALSPlan / run_hals).  update_H=False takes W_shard=None and starts from W = 0.  No weights,
+    sum_to_one / smoothness or bf16 X, and no in-launch exchange: 'auto' takes the all-reduce path,
+    exchange=True warns and takes it.  n_iter is sklearn's (the iterations run before the stop).
     """
     if exchange not in ("auto", True, False):
         raise ValueError(f"exchange must be 'auto', True or False, got {exchange!r}")
+    if solver not in ("mu", "als", "hals"):
+        raise ValueError(f"solver must be 'mu', 'als' or 'hals', got {solver!r}")
+    if solver == "hals":  # refused as cnmf_amd.factorise refuses them, before any device work
+        if weights is not None:
+            raise ValueError("weights apply to solver='mu' only")
+        if sum_to_one or smoothness:
+            raise ValueError("sum_to_one / smoothness apply to solver='als' only")
+        if torch.as_tensor(X_shard).dtype == torch.bfloat16:
+            raise TypeError("bfloat16 X is not available for solver='hals': pass float32 or float64")
+        if W_shard is None and update_H:
+            raise ValueError("W_shard=None is the update_H=False start (W = 0); a fit needs W_shard")
     if not (dist.is_available() and dist.is_initialized()):
         raise RuntimeError("factorise_sharded needs an initialised torch.distributed process group")
     group = group if group is not None else dist.group.WORLD
@@ -73,8 +92,20 @@ def factorise_sharded(X_shard, W_shard, H0, *, max_iter=200, tol=1e-4, l1_reg_W=
     X = torch.as_tensor(X_shard).to(dev).contiguous()
     H0 = torch.as_tensor(H0).to(dev, torch.float64).contiguous()
     dist.broadcast(H0, src=dist.get_global_rank(group, 0), group=group)
-    if solver not in ("mu", "als"):
-        raise ValueError(f"solver must be 'mu' or 'als', got {solver!r}")
+    if solver == "hals":
+        plan = HALSPlan(X, H0.shape[0], l1_reg_W, l2_reg_W, l1_reg_H, l2_reg_H, group=group)
+        if W_shard is None:  # the update_H=False start (SK:1228-1235)
+            plan.W.zero_()
+        else:
+            plan.set_W(torch.as_tensor(W_shard))
+        plan.set_H(H0)
+        if exchange is True:  # 'auto' takes the all-reduce path silently: there is no other
+            try:
+                plan.enable_exchange()
+            except _lib.HipLibraryError as e:
+                warnings.warn(f"in-launch exchange not used: {e}", RuntimeWarning)
+        n_iter = run_hals(plan, max_iter=max_iter, tol=tol, update_H=update_H)
+        return plan.W, plan.H(), n_iter
     if weights is not None or solver == "als":
         if any((l1_reg_W, l2_reg_W, l1_reg_H, l2_reg_H)):
             raise ValueError("the weighted MU and the constrained ALS take no l1/l2 regularisation")

@@ -773,13 +773,16 @@ class HALSPlan(MUPlan):
     stopping rule — is ONE launch (cnmf_hals_step, csrc/hals.hip); a stop sets a word on the device
     that turns every later launch into a no-op.  MUPlan's X / W / H64 / Ht / HHt state, set_W, set_H,
     refresh_basis and normalise are reused; the partial rows, the ticket word, the control block
-    and the loss launch behind frobenius_error (cnmf_hals_loss) are the plan's own.  fp32 / fp64
-    X, one device."""
+    and the loss launch behind frobenius_error (cnmf_hals_loss) are the plan's own.  fp32 / fp64 X.
+
+    Row shards (`group` of more than one rank: X is this rank's rows, H64 / Ht / HHt and the control
+    block are replicated) run the split form of the iteration: cnmf_hals_shard_step leaves the
+    shard's summed row [W'ᵀX | W'ᵀW' | Σ|pg|] in `acc`, one all-reduce sums it over the ranks, and
+    cnmf_hals_basis applies the H-sweep and the stopping rule — the same on every rank, so H and
+    the decision to stop are identical everywhere.  split=True selects that form on one rank."""
 
     def __init__(self, X: torch.Tensor, n_components: int, l1_W=0.0, l2_W=0.0, l1_H=0.0, l2_H=0.0,
-                 group=None):
-        if group is not None and plan_world(group) > 1:
-            raise ValueError("solver='hals' runs on one device (no sharded fit)")
+                 group=None, split: bool = False):
         if X.dtype == torch.bfloat16:
             raise TypeError("bfloat16 X is not available for solver='hals': pass float32 or float64")
         if X.device.type != "cuda":
@@ -798,7 +801,9 @@ class HALSPlan(MUPlan):
         self.xdt = _XDT[X.dtype]
         self.tc = X.dtype
         self.l1_W, self.l2_W, self.l1_H, self.l2_H = map(float, (l1_W, l2_W, l1_H, l2_H))
-        self.group, self.world = None, 1
+        self.world = plan_world(group)
+        self.group = group if self.world > 1 else None
+        self.split = bool(split) or self.world > 1
         self.hals_row_doubles = int(check(self.lib.cnmf_hals_row_doubles(self.F, self.k), "cnmf_hals_row_doubles"))
         self.hals_rows = int(check(self.lib.cnmf_hals_rows(self.n_rows), "cnmf_hals_rows"))
         self.KP = int(check(self.lib.cnmf_padded_k(self.k), "cnmf_padded_k"))
@@ -817,6 +822,8 @@ class HALSPlan(MUPlan):
                                          device=self.device)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.counter = self.ticket  # MUPlan.counters_at_rest
+        # the split form's summed row: what the ranks all-reduce between its two launches
+        self.acc = torch.zeros(self.hals_row_doubles, dtype=f64, device=dev) if self.split else None
         self.ctl = self.new_ctl()
 
     def new_ctl(self, tol: float = 0.0, log_cap: int = 0) -> torch.Tensor:
@@ -827,7 +834,25 @@ class HALSPlan(MUPlan):
         return torch.from_numpy(host).to(self.device)
 
     def step(self, update_H: bool = True):
-        """One SKCD iteration (a no-op once the control block's STOPPED word is set)."""
+        """One SKCD iteration (a no-op once the control block's STOPPED word is set).  The split form
+        enqueues its all-reduce whatever the gate does, so every rank makes the same collectives:
+        after a stop it moves a stale row that nobody reads."""
+        if self.split:
+            with torch.cuda.device(self.device):
+                if self.n_rows == 0:  # an empty shard contributes zeros to the all-reduce
+                    self.acc.zero_()
+                else:
+                    check(self.lib.cnmf_hals_shard_step(
+                        _ptr(self.X), self.xdt, _ptr(self.W), _ptr(self.Ht), _ptr(self.HHt),
+                        _ptr(self.hals_partials), self.hals_rows, _ptr(self.ticket), _ptr(self.ctl),
+                        _ptr(self.acc), self.n_rows, self.F, self.k, self.l1_W, self.l2_W, self._stream()),
+                        "cnmf_hals_shard_step")
+                self._allreduce(self.acc)
+                check(self.lib.cnmf_hals_basis(
+                    _ptr(self.acc), _ptr(self.H64), _ptr(self.Ht), _ptr(self.HHt), _ptr(self.ctl), self.F,
+                    self.k, self.l1_H, self.l2_H, HALS_UPDATE_H if update_H else 0, self._stream()),
+                    "cnmf_hals_basis")
+            return
         with torch.cuda.device(self.device):
             check(self.lib.cnmf_hals_step(
                 _ptr(self.X), self.xdt, _ptr(self.W), _ptr(self.H64), _ptr(self.Ht), _ptr(self.HHt),
@@ -841,12 +866,17 @@ class HALSPlan(MUPlan):
 
     def frobenius_error(self) -> float:
         """sqrt(‖X − W·H‖²) (SK:85-129) with the family's own loss launch (cnmf_hals_loss: the MU loss
-        pass does not take every row width the step serves); synchronises."""
+        pass does not take every row width the step serves); synchronises.  Row shards all-reduce
+        their ‖X_r − W_r·H‖² before the square root (collective)."""
         with torch.cuda.device(self.device):
-            check(self.lib.cnmf_hals_loss(_ptr(self.X), self.xdt, _ptr(self.W), _ptr(self.H64),
-                                          _ptr(self.hals_partials), self.hals_rows, _ptr(self.ticket),
-                                          _ptr(self.loss_buf), self.n_rows, self.F, self.k, self._stream()),
-                  "cnmf_hals_loss")
+            if self.n_rows == 0:
+                self.loss_buf.zero_()
+            else:
+                check(self.lib.cnmf_hals_loss(_ptr(self.X), self.xdt, _ptr(self.W), _ptr(self.H64),
+                                              _ptr(self.hals_partials), self.hals_rows, _ptr(self.ticket),
+                                              _ptr(self.loss_buf), self.n_rows, self.F, self.k, self._stream()),
+                      "cnmf_hals_loss")
+            self._allreduce(self.loss_buf)
         return math.sqrt(max(float(self.loss_buf.item()), 0.0))
 
     def iterate(self, n_iter: int, update_H: bool = True, pass_events=None):
@@ -857,7 +887,8 @@ class HALSPlan(MUPlan):
             self.step(update_H)
 
     def enable_exchange(self):
-        raise _lib.HipLibraryError("solver='hals' has no in-launch exchange: it runs on one device")
+        raise _lib.HipLibraryError("solver='hals' has no in-launch exchange: row shards all-reduce between "
+                                   "the iteration's two launches")
 
     def prepare_device_tol(self, max_iter, tol, pass_events=None):
         return None  # run_hals is the driver: the rule is on the device in every launch
@@ -866,6 +897,10 @@ class HALSPlan(MUPlan):
         return {}  # one kernel
 
     def describe(self) -> str:
+        if self.split:
+            return ("hals_shard_step_kernel + all-reduce + hals_basis_kernel per iteration (the W-sweep per "
+                    "sample in fp64 and the shard's summed fp64 row; then, identical on every rank, the H-sweep "
+                    "and the stopping rule)")
         return ("hals_step_kernel: one launch per iteration (the W-sweep per sample in fp64, the fp64 partial "
                 "rows, the last-arriving workgroup's H-sweep and stopping rule)")
 
@@ -890,6 +925,16 @@ def run_hals(plan: HALSPlan, max_iter: int = 200, tol: float = 1e-4, update_H: b
                 plan.step(update_H)
         launched += n
         host = plan.read_ctl()
+        if plan.world > 1:
+            # every rank ran the same rule on the same sums; a rank that differs would enqueue other
+            # collectives from here on, so it is an error on every rank instead of a hang
+            mine = [host[HALS_STOPPED], host[HALS_ITERS_DONE]]
+            top = agree_max(mine + [-v for v in mine], plan.group, plan.device)  # the maxima, then minus the minima
+            if top[0] != -top[2] or top[1] != -top[3]:
+                raise _lib.HipLibraryError(
+                    "solver='hals': the ranks disagree on (STOPPED, ITERS_DONE): this rank "
+                    f"({int(mine[0])}, {int(mine[1])}), over the ranks max ({int(top[0])}, {int(top[1])}) "
+                    f"min ({int(-top[2])}, {int(-top[3])})")
         if verbose and host[HALS_VIOL_INIT] != 0:
             for i in range(printed, int(host[HALS_NLOG])):
                 print("violation:", host[HALS_LOG + i] / host[HALS_VIOL_INIT])

@@ -51,7 +51,8 @@ enum cnmf_pass_flags {
 };
 
 /* ABI version (major*100 + minor) and last error message of the calling thread.  303 also covers
- * the cnmf_hals_* entry points: they only add symbols, no existing signature or layout changed. */
+ * the cnmf_hals_* entry points (cnmf_hals_shard_step and cnmf_hals_basis among them): they only add
+ * symbols, no existing signature or layout changed. */
 int cnmf_abi_version(void);
 const char* cnmf_last_error(void);
 
@@ -468,6 +469,27 @@ int64_t cnmf_hals_ctl_doubles(int64_t log_cap);
 int cnmf_hals_step(const void* X, int x_dtype, void* W, double* H64, double* Ht, double* HHt, double* partials,
                    int64_t n_parts, uint32_t* counter, double* ctl, int64_t n_rows, int n_features, int k,
                    double l1_W, double l2_W, double l1_H, double l2_H, int flags, void* stream);
+/* The iteration over row shards (one rank per GPU; X, W: this rank's n_rows rows; H64 / Ht / HHt / ctl
+ * replicated): cnmf_hals_shard_step, an all-reduce (sum) of acc over the ranks by the caller, then
+ * cnmf_hals_basis.  On one rank the two launches give the bits of cnmf_hals_step when n_features <=
+ * 256 or the step's workgroup has 256 threads (always for k > 8); otherwise W, H64, Ht and HHt of an
+ * iteration are still the step's, and only the last bits of the H-sweep's share of the violation can
+ * differ (its sum is taken by 256 threads here, whatever the shard's rows: the same on every rank).
+ * cnmf_hals_shard_step: the gate, the W-sweep and the partial rows as cnmf_hals_step (the same
+ *   shapes and argument checks); the last-arriving workgroup sums the rows in row order into
+ *   acc[cnmf_hals_row_doubles(F, k)] = [W'^T X | W'^T W' | sum |pg| | pad] and stops: no H-sweep, nothing
+ *   written to H64 / Ht / HHt / ctl; counter is left zero.  acc: 16-byte aligned.  A rank without rows
+ *   makes no launch and zeroes acc.
+ * cnmf_hals_basis: one workgroup; the gate, then cnmf_hals_step's tail from the all-reduced acc: with
+ *   CNMF_HALS_UPDATE_H the H-sweep and H64 / Ht / HHt refreshed; always violation = acc's sum |pg| + the
+ *   H-sweep's, ITERS_DONE, VIOL_INIT, VIOL_LAST, the log and STOPPED (flags = 0: the rule alone, on the
+ *   violation of all rows).  The same acc, H64 and ctl give the same bits on every rank.  Once
+ *   STOPPED is set both launches write nothing, whatever acc then holds. */
+int cnmf_hals_shard_step(const void* X, int x_dtype, void* W, const double* Ht, const double* HHt, double* partials,
+                         int64_t n_parts, uint32_t* counter, const double* ctl, double* acc, int64_t n_rows,
+                         int n_features, int k, double l1_W, double l2_W, void* stream);
+int cnmf_hals_basis(const double* acc, double* H64, double* Ht, double* HHt, double* ctl, int n_features, int k,
+                    double l1_H, double l2_H, int flags, void* stream);
 /* out[0] = ||X - W H||^2 (SK:85-129 before the square root) in fp64 from H64, for every shape
  * cnmf_hals_step serves (cnmf_mu_sample_pass's loss form does not take rows as wide: F = 300 at
  * k = 16 in fp64, F = 512).  partials: cnmf_hals_rows(n_rows) doubles (the step's buffer will do);

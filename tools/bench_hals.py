@@ -3,6 +3,9 @@
 per-iteration (default): µs per cnmf_hals_step launch against the per-iteration MU sequence it stands
     beside (cnmf_mu_sample_pass + cnmf_reduce_update over the same rows), alternated in the same
     process, at each `--shapes` entry (rows,features,k; fp32).
+--split: µs per iteration of the sharded form on one rank (cnmf_hals_shard_step + cnmf_hals_basis, two
+    launches, no all-reduce) against the one cnmf_hals_step launch, alternated in the same process at
+    each `--shapes` entry: the price of the split.
 --time-to-error: on rows x 81, k = 4 from random_init, the error and device time of `--mu-iters`
     iterations of the default MU fit (the persistent wave-tile launch), then the iterations and the
     device time solver='hals' needs to reach that error.
@@ -84,6 +87,40 @@ def per_iteration(a, out):
         del hals, mu, Xd
 
 
+def split_price(a, out):
+    """The one launch against the split form (shard step + basis launch; one rank, so no all-reduce)."""
+    import torch
+    from cnmf_amd.solver import HALSPlan
+    from cnmf_amd.synthetic import iop_spectra, random_init
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stream = torch.cuda.current_stream(dev)
+    for shape in a.shapes:
+        n, F, k = (int(v) for v in shape.split(","))
+        X = iop_spectra(n, F, seed=0, dtype=np.float32)
+        W0, H0 = random_init(X, k, 42)
+        Xd = torch.from_numpy(X).to(dev)
+        one, split = HALSPlan(Xd, k), HALSPlan(Xd, k, split=True)
+        for p in (one, split):
+            p.set_W(torch.from_numpy(W0))
+            p.set_H(torch.from_numpy(H0))
+            p.ctl = p.new_ctl(tol=0.0)  # never stops: every launch does the work
+        for _ in range(a.warm):
+            one.step()
+            split.step()
+        torch.cuda.synchronize()
+        t_o, t_s = [], []
+        for _ in range(a.repeats):
+            t_o.append(window_ms(one.step, a.reps, stream) / a.reps * 1e3)
+            t_s.append(window_ms(split.step, a.reps, stream) / a.reps * 1e3)
+        assert one.read_ctl()[0] == 0.0 and split.read_ctl()[0] == 0.0, "the timed launches were no-ops"
+        same = all(torch.equal(x, y) for x, y in ((one.W, split.W), (one.H64, split.H64), (one.ctl, split.ctl)))
+        out[f"split_{n}x{F}_k{k}"] = {
+            "one_launch": summary(t_o), "split": summary(t_s), "same_bits": same,
+            "extra_us": round(statistics.median(t_s) - statistics.median(t_o), 2),
+            "ratio_split_over_one": round(statistics.median(t_s) / statistics.median(t_o), 4)}
+        del one, split, Xd
+
+
 def time_to_error(a, out):
     import torch
     from cnmf_amd.solver import HALSPlan, MUPlan
@@ -144,6 +181,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="+", default=["1000000,81,4", "200000,300,16"])
     ap.add_argument("--time-to-error", action="store_true")
+    ap.add_argument("--split", action="store_true")
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--mu-iters", type=int, default=500)
     ap.add_argument("--max-hals-iters", type=int, default=200)
@@ -157,6 +195,8 @@ def main():
     out = {"warm": a.warm, "reps": a.reps, "repeats": a.repeats}
     if a.time_to_error:
         time_to_error(a, out)
+    elif a.split:
+        split_price(a, out)
     else:
         per_iteration(a, out)
     print(json.dumps(out), flush=True)
