@@ -132,6 +132,13 @@ _SIGS = {
     "cnmf_spa_ctl_doubles": (_i64, [_i32]),
     "cnmf_spa_step": (_i32, [_vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "cnmf_spa_start_w": (_i32, [_vp, _i32, _vp, _f64, _vp, _i32, _i64, _i32, _i32, _vp]),
+    "cnmf_ms_batch": (_i32, [_i32, _i32, _i32]),
+    "cnmf_ms_rows": (_i64, [_i64]),
+    "cnmf_ms_row_doubles": (_i64, [_i32, _i32, _i32]),
+    "cnmf_ms_ctl_doubles": (_i64, [_i32]),
+    "cnmf_ms_step": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32,
+                            _f64, _f64, _f64, _f64, _i32, _vp]),
+    "cnmf_ms_loss": (_i32, [_vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
 }
 
 

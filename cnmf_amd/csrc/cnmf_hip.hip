@@ -7913,4 +7913,5 @@ int cnmf_wmu_basis_update(const double* AD, double* H64, int n_features, int k, 
 #include "minibatch.hip"
 #include "hals.hip"
 #include "spa.hip"
+#include "multistart.hip"
 #endif

@@ -540,6 +540,54 @@ int cnmf_spa_step(const void* X, int x_dtype, double* Q, double* partials, int64
 int cnmf_spa_start_w(const void* X, int x_dtype, const double* M, double floor, void* W, int w_dtype, int64_t n_rows,
                      int n_features, int k, void* stream);
 
+/* ---- factorise_multistart: R independent starts of solver='hals' on the same X, an iteration of up
+ * to cnmf_ms_batch(F, k, x_dtype) of them (a batch) in ONE launch that stages every tile of X once
+ * (cnmf_amd/multistart.py).  fp32 or fp64 X, W in X's type, 1 <= k <= 16,
+ * 1 <= n_features <= 512, any n_rows >= 1, one GPU.  Per start the arithmetic is cnmf_hals_step's spec
+ * (the sweep above, tests/hals_ref.py).
+ *
+ * Layouts, start-major, so every start's factors are plain contiguous matrices:
+ *   W [n_starts][n_rows][k] in X's type; H64 [n_starts][k][F]; Ht [n_starts][F][KP] and HHt
+ *   [n_starts][KP][KP] per start as cnmf_hals_step's (KP = cnmf_padded_k(k), zero beyond k);
+ *   ctl: cnmf_ms_ctl_doubles(n_starts) doubles, CNMF_MS_STRIDE per start with the cnmf_hals_slots
+ *   meanings at the cnmf_ms_slots offsets; zeroed by the caller, who then sets every start's
+ *   CNMF_MS_TOL; the launches maintain the rest;
+ *   partials: cnmf_ms_rows(n_rows) rows of cnmf_ms_row_doubles(F, k, n_starts) doubles (per start
+ *   [W'^T X | W'^T W' | sum |pg| | pad]; no memset needed); counter: one zeroed uint32, left zero.
+ * The gate: every launch first reads the STOPPED word of every start of the batch.  If all are set it
+ *   writes nothing.  A start whose word is set is skipped for the whole launch: its W, H64, Ht, HHt,
+ *   partial rows and control words keep their bits.
+ * cnmf_ms_step: for every live start one SKCD iteration as cnmf_hals_step: the W-sweep of every sample
+ *   in fp64, w' rounded once to W's type; with CNMF_MS_UPDATE_H the H-sweep, H64 / Ht / HHt refreshed;
+ *   ITERS_DONE advances; iteration 1 stores VIOL_INIT; STOPPED is set when VIOL_INIT == 0 or violation /
+ *   VIOL_INIT <= TOL (every iteration, also for TOL = 0).  Nothing waits for another workgroup.  The
+ *   same inputs give the same bits.
+ * Independence: the operations that produce start r, and their order, depend on (n_rows, F, k, X's
+ *   type) alone: not on n_starts, on the position of the start in the batch, on the other starts'
+ *   values or on whether they have stopped.  A start gives the same bits alone as in any batch.
+ * cnmf_ms_loss: out[r] = ||X - W_r H_r||^2 in fp64 (cnmf_hals_loss's arithmetic per start, fixed-order
+ *   sums) for the n_starts starts in one pass over X; partials: cnmf_ms_rows(n_rows) * n_starts
+ *   doubles (the step's buffer will do); the STOPPED words are not read.
+ * n_starts <= cnmf_ms_batch(F, k, x_dtype) for both launches.  cnmf_ms_batch returns 1 at every shape in
+ *   this build: the batched form of the step measured slower than as many one-start launches (DESIGN.md
+ *   §3.12), so a launch takes one start, which cnmf_ms_step hands to cnmf_hals_step; callers size
+ *   their batches by the helper and need no change when it returns more.  The sizing helpers are host
+ *   only. */
+enum cnmf_ms_flags { CNMF_MS_UPDATE_H = 1 };
+enum cnmf_ms_slots {
+  CNMF_MS_STOPPED = 0, CNMF_MS_ITERS_DONE = 1, CNMF_MS_VIOL_INIT = 2, CNMF_MS_VIOL_LAST = 3, CNMF_MS_TOL = 4,
+  CNMF_MS_STRIDE = 8
+};
+int cnmf_ms_batch(int n_features, int k, int x_dtype);
+int64_t cnmf_ms_rows(int64_t n_rows);
+int64_t cnmf_ms_row_doubles(int n_features, int k, int n_starts);
+int64_t cnmf_ms_ctl_doubles(int n_starts);
+int cnmf_ms_step(const void* X, int x_dtype, void* W, double* H64, double* Ht, double* HHt, double* partials,
+                 int64_t n_parts, uint32_t* counter, double* ctl, int64_t n_rows, int n_features, int k, int n_starts,
+                 double l1_W, double l2_W, double l1_H, double l2_H, int flags, void* stream);
+int cnmf_ms_loss(const void* X, int x_dtype, const void* W, const double* H64, double* partials, int64_t n_parts,
+                 uint32_t* counter, double* out, int64_t n_rows, int n_features, int k, int n_starts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
