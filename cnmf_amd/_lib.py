@@ -127,6 +127,11 @@ _SIGS = {
                                     _f64, _f64, _vp]),
     "cnmf_hals_basis": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f64, _f64, _i32, _vp]),
     "cnmf_hals_loss": (_i32, [_vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp]),
+    "cnmf_whals_rows": (_i64, [_i64]),
+    "cnmf_whals_row_doubles": (_i64, [_i32, _i32]),
+    "cnmf_whals_step": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32,
+                               _f64, _f64, _f64, _f64, _i32, _vp]),
+    "cnmf_whals_loss": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp]),
     "cnmf_spa_rows": (_i64, [_i64]),
     "cnmf_spa_row_doubles": (_i64, []),
     "cnmf_spa_ctl_doubles": (_i64, [_i32]),

@@ -11,7 +11,8 @@ scikit-learn 1.7.2's Frobenius MU path (SK = sklearn/decomposition/_nmf.py):
 Differences, all deliberate: the solvers are 'mu' (the default here; sklearn's default 'cd'
 raises), the build's constrained ALS 'als' (sum_to_one / smoothness; k ≤ 8) and
 'hals' — sklearn's 'cd' algorithm itself (`_fit_coordinate_descent`, SK:376-523, shuffle=False:
-the Fast HALS sweep and its stopping rule; fp32 / fp64 X on one device; the name 'cd' stays refused),
+the Fast HALS sweep and its stopping rule; fp32 / fp64 X on one device; the name 'cd' stays refused)
+with 'whals', the same sweep for weighted / masked X (weights= required),
 only beta_loss='frobenius' is accepted, sparse X is not, and n_components ≤ 16.  normalise=
 ('l1' | 'l2' | 'max') adds the §8 a6 projection (off by default, so 'mu' output is sklearn's).  NumPy
 inputs are copied to the GPU and results come back as NumPy arrays of X's dtype; torch tensors on a
@@ -123,10 +124,10 @@ def _validate_params(n_components, init, solver, beta_loss, tol, max_iter, alpha
     if init not in _INITS:
         raise ValueError(f"The 'init' parameter must be a str among {{'custom', 'nndsvd', "
                          f"'nndsvda', 'nndsvdar', 'random', 'spa'}} or None. Got {init!r} instead.")
-    if solver not in ("mu", "als", "hals"):
+    if solver not in ("mu", "als", "hals", "whals"):
         raise ValueError(f"solver={solver!r} is not available: this build implements the "
                          "multiplicative-update solver ('mu') and the constrained ALS ('als'), "
-                         "and HALS ('hals').")
+                         "and HALS ('hals') with its weighted form ('whals').")
     if beta_loss not in ("frobenius", 2, 2.0):
         raise ValueError(f"beta_loss={beta_loss!r} is not available: only 'frobenius' (2) is "
                          "implemented on the MI355X path.")
@@ -157,6 +158,9 @@ def _compute_regularization(n_samples, n_features, alpha_W, alpha_H, l1_ratio):
 def _validate_als(solver, alpha_W, alpha_H, sum_to_one, smoothness):
     if solver != "als":
         if sum_to_one is not None or smoothness:
+            if solver == "whals":
+                raise ValueError("sum_to_one / smoothness are not available for solver='whals': they apply "
+                                 "to solver='als' only")
             raise ValueError("sum_to_one / smoothness apply to solver='als' only")
         return
     if alpha_W != 0 or alpha_H not in ("same", 0, 0.0):
@@ -171,6 +175,8 @@ def _validate_als(solver, alpha_W, alpha_H, sum_to_one, smoothness):
 def _validate_weights(weights, X, solver, alpha_W, alpha_H, normalise):
     """Weighted / masked MU: per-element weights of X's shape, finite and
     non-negative, float32 X; solver 'mu' without alpha regularisation or normalise."""
+    if solver == "whals":
+        return _validate_whals_weights(weights, X, normalise)
     if weights is None:
         return None
     if solver != "mu":
@@ -190,15 +196,35 @@ def _validate_weights(weights, X, solver, alpha_W, alpha_H, normalise):
     return Mw
 
 
+def _validate_whals_weights(weights, X, normalise):
+    """solver='whals' (weighted / masked HALS): weights of X's shape, finite and
+    non-negative, are required; float32 / float64 X; alpha regularisation is taken, normalise is
+    not."""
+    if weights is None:
+        raise ValueError("solver='whals' needs weights= (an array of X's shape, >= 0): for an unweighted X use "
+                         "solver='hals', the same sweep without them")
+    if normalise is not None:
+        raise ValueError("normalise is not available for solver='whals'")
+    if _is_torch(X) and X.dtype == _torch().bfloat16:
+        raise TypeError("bfloat16 X is not available for solver='whals': pass float32 or float64")
+    Mw = _check_X(weights)
+    if tuple(Mw.shape) != tuple(X.shape):
+        raise ValueError(f"weights must have X's shape {tuple(X.shape)}, got {tuple(Mw.shape)}")
+    if _min(Mw) < 0:
+        raise ValueError("Negative values in data passed to NMF (input weights)")
+    return Mw
+
+
 def _validate_hals(solver, shuffle, devices=None):
-    """solver='hals' (sklearn's 'cd' sweep, SK:376-523) runs the cyclic order on one device."""
-    if solver != "hals":
+    """solver='hals' (sklearn's 'cd' sweep, SK:376-523) and its weighted form 'whals' run the cyclic
+    order on one device."""
+    if solver not in ("hals", "whals"):
         return
     if shuffle:
-        raise ValueError("shuffle=True is not available for solver='hals': the sweep visits the "
+        raise ValueError(f"shuffle=True is not available for solver='{solver}': the sweep visits the "
                          "components in cyclic order (sklearn's shuffle=False).")
     if devices is not None:
-        raise ValueError("devices= is not available for solver='hals': it runs on one device.")
+        raise ValueError(f"devices= is not available for solver='{solver}': it runs on one device.")
 
 
 def _validate_spa(init, weights=None, devices=None, group=None, streamed=False):
@@ -233,6 +259,9 @@ def _streamed(X, as_torch, memory_budget, solver, Mw):
     nbytes = X.numel() * X.element_size() if as_torch else X.nbytes
     if nbytes <= memory_budget:
         return False
+    if solver == "whals":
+        raise ValueError("a memory_budget that streams X is not available for solver='whals': X and the "
+                         "weights stay on the device")
     if solver != "mu" or Mw is not None:
         raise ValueError("memory_budget (out-of-core streaming) serves the unweighted 'mu' solver")
     if as_torch and X.dtype not in (_torch().float32, _torch().float64):
@@ -293,6 +322,8 @@ def _resolve(X, W, H, n_components, init, update_H, alpha_W, alpha_H, l1_ratio, 
     (X, Mw, as_torch, streamed, k, W, H, regs); W is None for the update_H=False start."""
     torch = _torch()
     X = _check_X(X)
+    if solver == "whals" and group is not None:
+        raise ValueError("solver='whals' is not available for a sharded fit (group=): it runs on one device.")
     Mw = _validate_weights(weights, X, solver, alpha_W, alpha_H, normalise)
     as_torch = _is_torch(X)
     if solver == "hals" and as_torch and X.dtype == torch.bfloat16:
@@ -342,7 +373,10 @@ def _resolve(X, W, H, n_components, init, update_H, alpha_W, alpha_H, l1_ratio, 
         raise ValueError(f"n_components={k} is not supported: the MI355X kernels handle 1..16.")
     if solver == "als" and k > 8:
         raise ValueError(f"n_components={k} is not supported by solver='als' (1..8).")
-    if Mw is not None and k > 8:
+    if solver == "whals":
+        from .solver import whals_row_doubles
+        whals_row_doubles(n_features, k)  # a shape it does not serve: a ValueError naming k and F
+    elif Mw is not None and k > 8:
         raise ValueError(f"n_components={k} is not supported by the weighted MU (1..8).")
     regs = _compute_regularization(n_samples, n_features, alpha_W, alpha_H, l1_ratio)
     return X, Mw, as_torch, streamed, k, W, H, regs
@@ -352,13 +386,16 @@ def _make_plan(X, Mw, k, regs, dev, *, solver="mu", sum_to_one=None, smoothness=
                streamed=False, memory_budget=None):
     """The plan (device state + launches) that runs the fit of X (all of it, or one shard)."""
     torch = _torch()
-    from .solver import ALSPlan, HALSPlan, MUPlan, WeightedMUPlan
+    from .solver import ALSPlan, HALSPlan, MUPlan, WeightedHALSPlan, WeightedMUPlan
     if streamed:  # §8 f3: X stays in host memory and streams through a memory_budget of HBM
         from .outofcore import StreamedMUPlan
         return StreamedMUPlan(X, k, regs[0], regs[2], regs[1], regs[3], group=group, device=dev,
                               memory_budget=memory_budget)
     Xd = X if _is_torch(X) else torch.from_numpy(np.ascontiguousarray(X))
     Xd = Xd.to(dev, non_blocking=False).contiguous()
+    if solver == "whals":
+        Md = (Mw if _is_torch(Mw) else torch.from_numpy(np.ascontiguousarray(Mw))).to(dev, Xd.dtype).contiguous()
+        return WeightedHALSPlan(Xd, Md, k, regs[0], regs[2], regs[1], regs[3])
     if Mw is not None:
         Md = (Mw if _is_torch(Mw) else torch.from_numpy(np.ascontiguousarray(Mw))).to(dev, torch.float32).contiguous()
         return WeightedMUPlan(Xd, Md, k, group=group)
@@ -404,10 +441,10 @@ def _fit_transform(X, W, H, n_components, init, update_H, tol, max_iter, alpha_W
                       group=group, streamed=streamed, memory_budget=memory_budget)
     avg = None
     if W is None:  # the update_H=False start; sklearn's non-'mu' branch is zeros (SK:1233-1235)
-        avg = 0.0 if solver == "hals" else _transform_start(X, as_torch, k)
+        avg = 0.0 if solver in ("hals", "whals") else _transform_start(X, as_torch, k)
     _start(plan, W, H, avg)
     try:
-        run = run_hals if solver == "hals" else run_mu
+        run = run_hals if solver in ("hals", "whals") else run_mu
         n_iter = run(plan, max_iter=max_iter, tol=tol, update_H=update_H, verbose=verbose)
         if n_iter == max_iter and tol > 0:
             warnings.warn("Maximum number of iterations %d reached. Increase it to improve "
@@ -463,6 +500,13 @@ def factorise(X, W=None, H=None, n_components="auto", *, init=None, update_H=Tru
     to tol times its first value (tested every iteration).  One launch per iteration, the rule on
     the device.  float32 / float64 X on one device; no weights, memory_budget streaming, devices=
     or shuffle=True.  The update_H=False start is W = 0, as sklearn's.
+    solver='whals' is that sweep for weighted / masked X (`weights` required; tests/whals_ref.py):
+    the objective is ½ Σ m·(x − wh)² plus the alpha terms, the Gram matrix per sample in the W-sweep
+    and per feature in the H-sweep; a row or column whose weights are all zero keeps its start.
+    float32 / float64 X (the weights are cast to X's dtype), k <= 4 with up to 512 features or
+    k <= 8 with up to 192, one device; no shuffle=True, devices=, shards, streaming, normalise,
+    sum_to_one / smoothness or init='spa'.  Masked new data against a fixed H:
+    factorise(X, H=H, update_H=False, weights=M, solver='whals').
     `weights` (array of X's shape, >= 0; None = off) selects the weighted / masked MU (SURVEY.md
     §8(f) row 2, oracle/wmu_ref.py): the loss becomes Σ m·(x − wh)², so a weight 0 marks a missing
     value (give X any finite non-negative entry there) and 1/σ² an uncertainty weight; float32 X,
@@ -601,7 +645,8 @@ class NMF:
         W, _, _ = _fit_transform(X, None, self.components_, self.n_components_, self.init, False,
                                  self.tol, self.max_iter, self.alpha_W, self.alpha_H,
                                  self.l1_ratio, self.random_state, self.verbose, self.device,
-                                 solver=self.solver, sum_to_one=self.sum_to_one,
+                                 solver="hals" if self.solver == "whals" else self.solver,  # unit weights
+                                 sum_to_one=self.sum_to_one,
                                  smoothness=self.smoothness, memory_budget=self.memory_budget)
         return W
 

@@ -7914,4 +7914,5 @@ int cnmf_wmu_basis_update(const double* AD, double* H64, int n_features, int k, 
 #include "hals.hip"
 #include "spa.hip"
 #include "multistart.hip"
+#include "whals.hip"
 #endif

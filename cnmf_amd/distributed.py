@@ -74,6 +74,9 @@ def factorise_sharded(X_shard, W_shard, H0, *, max_iter=200, tol=1e-4, l1_reg_W=
     """
     if exchange not in ("auto", True, False):
         raise ValueError(f"exchange must be 'auto', True or False, got {exchange!r}")
+    if solver == "whals":
+        raise ValueError("solver='whals' is not available for a sharded fit (factorise_sharded): it runs on one "
+                         "device.")
     if solver not in ("mu", "als", "hals"):
         raise ValueError(f"solver must be 'mu', 'als' or 'hals', got {solver!r}")
     if solver == "hals":  # refused as cnmf_amd.factorise refuses them, before any device work

@@ -804,8 +804,7 @@ class HALSPlan(MUPlan):
         self.world = plan_world(group)
         self.group = group if self.world > 1 else None
         self.split = bool(split) or self.world > 1
-        self.hals_row_doubles = int(check(self.lib.cnmf_hals_row_doubles(self.F, self.k), "cnmf_hals_row_doubles"))
-        self.hals_rows = int(check(self.lib.cnmf_hals_rows(self.n_rows), "cnmf_hals_rows"))
+        self.hals_row_doubles, self.hals_rows = self._partial_rows()
         self.KP = int(check(self.lib.cnmf_padded_k(self.k), "cnmf_padded_k"))
         self.V = self.F + self.k
         self.n_out = self.k * self.V
@@ -825,6 +824,11 @@ class HALSPlan(MUPlan):
         # the split form's summed row: what the ranks all-reduce between its two launches
         self.acc = torch.zeros(self.hals_row_doubles, dtype=f64, device=dev) if self.split else None
         self.ctl = self.new_ctl()
+
+    def _partial_rows(self):
+        """(doubles per partial row, partial rows) of the step's launch."""
+        return (int(check(self.lib.cnmf_hals_row_doubles(self.F, self.k), "cnmf_hals_row_doubles")),
+                int(check(self.lib.cnmf_hals_rows(self.n_rows), "cnmf_hals_rows")))
 
     def new_ctl(self, tol: float = 0.0, log_cap: int = 0) -> torch.Tensor:
         """A zeroed control block with TOL and LOG_CAP set."""
@@ -944,6 +948,75 @@ def run_hals(plan: HALSPlan, max_iter: int = 200, tol: float = 1e-4, update_H: b
                 print("Converged at iteration", int(host[HALS_ITERS_DONE]) + 1)
             break
     return int(host[HALS_ITERS_DONE]) if host is not None else 0
+
+
+def whals_row_doubles(n_features: int, k: int) -> int:
+    """cnmf_whals_row_doubles (host only), a shape outside the served envelope as a ValueError."""
+    n = int(_lib.load().cnmf_whals_row_doubles(int(n_features), int(k)))
+    if n == -3:
+        raise ValueError(f"solver='whals' does not serve n_components k={k} with n_features F={n_features}: "
+                         "it takes 1 <= k <= 4 with F <= 512 and 5 <= k <= 8 with F <= 192")
+    return int(check(n, "cnmf_whals_row_doubles"))
+
+
+class WeightedHALSPlan(HALSPlan):
+    """Device state of solver='whals': HALSPlan's sweep for the weighted objective Σ m·(x − wh)²
+    (spec: tests/whals_ref.py).  The weights M (X's shape and type, >= 0) make the
+    Gram matrix of the W-sweep per sample and that of the H-sweep per feature, so HHᵀ has no role in
+    the step (the buffer stays, written by set_H's shared launch and never read):
+    one launch per iteration (cnmf_whals_step, csrc/whals.hip) reads Hᵀ, sweeps every sample against
+    its own H·diag(m_i)·Hᵀ, and its last workgroup sweeps every feature against its own
+    W'ᵀ·diag(m_:f)·W'.  HALSPlan's X / W / H64 / Ht, control block, ticket, step / read_ctl protocol
+    (run_hals drives it unchanged) are kept; frobenius_error is the weighted error sqrt(Σ m r²).
+    fp32 / fp64 X on one device; 1 <= k <= 4 with F <= 512, 5 <= k <= 8 with F <= 192."""
+
+    def __init__(self, X: torch.Tensor, M: torch.Tensor, n_components: int, l1_W=0.0, l2_W=0.0, l1_H=0.0,
+                 l2_H=0.0):
+        if X.dtype == torch.bfloat16:
+            raise TypeError("bfloat16 X is not available for solver='whals': pass float32 or float64")
+        if X.dim() != 2 or tuple(M.shape) != tuple(X.shape):
+            raise ValueError(f"weights must have X's shape {tuple(X.shape)}, got {tuple(M.shape)}")
+        if M.dtype != X.dtype:
+            raise TypeError(f"solver='whals' takes the weights in X's dtype {X.dtype}, got {M.dtype}")
+        if M.device != X.device:
+            raise ValueError("WeightedHALSPlan needs X and the weights on the same HIP device")
+        whals_row_doubles(X.shape[1], n_components)  # a shape it does not serve: before any device work
+        # HALSPlan's state with this family's partial rows (_partial_rows).  HHt stays allocated: set_H
+        # derives Ht with the launch every plan shares (cnmf_basis_update), which writes both; the
+        # step neither reads nor refreshes it.
+        super().__init__(X, n_components, l1_W, l2_W, l1_H, l2_H)
+        self.M = M.contiguous()
+
+    def _partial_rows(self):
+        return (whals_row_doubles(self.F, self.k),
+                int(check(self.lib.cnmf_whals_rows(self.n_rows), "cnmf_whals_rows")))
+
+    def step(self, update_H: bool = True):
+        """One iteration (a no-op once the control block's STOPPED word is set)."""
+        with torch.cuda.device(self.device):
+            check(self.lib.cnmf_whals_step(
+                _ptr(self.X), _ptr(self.M), self.xdt, _ptr(self.W), _ptr(self.H64), _ptr(self.Ht),
+                _ptr(self.hals_partials), self.hals_rows, _ptr(self.ticket), _ptr(self.ctl), self.n_rows,
+                self.F, self.k, self.l1_W, self.l2_W, self.l1_H, self.l2_H,
+                HALS_UPDATE_H if update_H else 0, self._stream()), "cnmf_whals_step")
+
+    def frobenius_error(self) -> float:
+        """The weighted error sqrt(Σ m·(x − wh)²), as the weighted MU reports it (cnmf_whals_loss);
+        synchronises."""
+        with torch.cuda.device(self.device):
+            check(self.lib.cnmf_whals_loss(_ptr(self.X), _ptr(self.M), self.xdt, _ptr(self.W), _ptr(self.H64),
+                                           _ptr(self.hals_partials), self.hals_rows, _ptr(self.ticket),
+                                           _ptr(self.loss_buf), self.n_rows, self.F, self.k, self._stream()),
+                  "cnmf_whals_loss")
+        return math.sqrt(max(float(self.loss_buf.item()), 0.0))
+
+    def normalise(self, norm: str = "l2"):
+        raise ValueError("normalise is not available for solver='whals'")
+
+    def describe(self) -> str:
+        return ("whals_step_kernel: one launch per iteration (per sample c_i and G_i = H diag(m_i) Ht in fp64 "
+                "against a table of h_a h_b in LDS, the W-sweep, the fp64 partial rows [A | S_f | sum|pg|], the "
+                "last-arriving workgroup's per-feature H-sweep and stopping rule)")
 
 
 class ALSPlan(MUPlan):

@@ -497,6 +497,38 @@ int cnmf_hals_basis(const double* acc, double* H64, double* Ht, double* HHt, dou
 int cnmf_hals_loss(const void* X, int x_dtype, const void* W, const double* H64, double* partials, int64_t n_parts,
                    uint32_t* counter, double* out, int64_t n_rows, int n_features, int k, void* stream);
 
+/* ---- solver='whals': the sweep above for weighted / masked X (cnmf_amd/solver.py WeightedHALSPlan,
+ * driven by run_hals; the spec is tests/whals_ref.py).  Objective: 1/2 sum_if
+ * m_if (x_if - sum_j w_ij h_jf)^2 plus the l1 / l2 terms; M >= 0 in X's type and shape, 0 = missing,
+ * 1/sigma^2 = an uncertainty weight.  fp32 or fp64 X, M and W in X's type, 1 <= k <= 8, n_features <=
+ * 512 for k <= 4 and <= 192 for 5 <= k <= 8, any n_rows >= 1, one GPU; cnmf_abi_version() stays 303
+ * (the entry points only add symbols).
+ *
+ * cnmf_whals_step: ONE launch = one iteration, with cnmf_hals_step's gate, control block (ctl:
+ *   cnmf_hals_ctl_doubles, cnmf_hals_slots), flag (CNMF_HALS_UPDATE_H) and stopping rule.  The W-sweep
+ *   runs per sample i against G_i = H diag(m_i) H^T (+ l2_W on the diagonal) and c_i = H (m_i o x_i) -
+ *   l1_W, both summed in fp64; w' is rounded once to W's type.  The H-sweep runs per feature f
+ *   against G_f = W'^T diag(m_:f) W' (+ l2_H) and c_f = W'^T (m_:f o x_:f) - l1_H and refreshes H64 and
+ *   Ht ([F][cnmf_padded_k(k)], zero beyond k; read at the start of the launch).  A row or column
+ *   whose weights are all zero keeps its factor row bit for bit (G[t,t] == 0) and adds no violation;
+ *   x under a zero weight is never used (any finite value).
+ *   partials: cnmf_whals_rows(n_rows) rows of cnmf_whals_row_doubles(F, k) doubles
+ *   [W'^T (M o X) (k F) | the upper triangle of W'^T diag(m_:f) W' (k(k+1)/2 rows of F) | sum |pg| | pad]
+ *   (no memset needed); counter: one zeroed uint32, left zero.  X, M and W: 16-byte aligned.
+ *   The same inputs give the same bits; launches after a stop write nothing.
+ * cnmf_whals_loss: out[0] = sum_if m_if (x_if - sum_j w_ij h_jf)^2 in fp64 from H64, fixed-order sums;
+ *   partials: cnmf_whals_rows(n_rows) doubles (the step's buffer will do).
+ * cnmf_whals_row_doubles: -2 for F or k < 1, -3 outside the shapes above.  The sizing helpers are
+ * host only. */
+int64_t cnmf_whals_rows(int64_t n_rows);
+int64_t cnmf_whals_row_doubles(int n_features, int k);
+int cnmf_whals_step(const void* X, const void* M, int x_dtype, void* W, double* H64, double* Ht, double* partials,
+                    int64_t n_parts, uint32_t* counter, double* ctl, int64_t n_rows, int n_features, int k,
+                    double l1_W, double l2_W, double l1_H, double l2_H, int flags, void* stream);
+int cnmf_whals_loss(const void* X, const void* M, int x_dtype, const void* W, const double* H64, double* partials,
+                    int64_t n_parts, uint32_t* counter, double* out, int64_t n_rows, int n_features, int k,
+                    void* stream);
+
 /* ---- init='spa': the successive projection algorithm (SPA; Araujo et al. 2001, Gillis & Vavasis
  * 2014) as a start: k rows of X, the "purest" spectra, become H0 (cnmf_amd/spa.py; the spec is
  * tests/spa_ref.py).  fp32 or fp64 X, 1 <= k <= 16, 1 <= n_features <= 512, any
